@@ -91,6 +91,68 @@ def cpu_baseline(cfg, sd, B, T, budget_s=25.0):
             "ms_per_step": 1e3 * el / n}
 
 
+def chain_segments(S, first, n):
+    """Steps first .. first + n - 1 of the S-step chain as [(t_start, n_steps)] runs: step i is timestep S - 1 - (i mod S), so a
+    range longer than the chain starts it again at t = S - 1."""
+    segs, i = [], first
+    while i < first + n:
+        t = S - 1 - i % S
+        k = min(t + 1, first + n - i)
+        segs.append((t, k))
+        i += k
+    return segs
+
+
+def chain_steps_fn(model, S, first, n, seed, verify=True, guard=True):
+    """dist.hip_steps_fn over steps first .. first + n - 1 of the chain (chain_segments).  Every run starts from the caller's x_T: a
+    range that wraps samples the chain again (the result is that of the last run); the weights are checksummed before the first
+    run and the runtime guard reads its monitors back after the last, as in one call."""
+    from egoego_release_amd import dist as D
+    segs = chain_segments(S, first, n)
+    fns = [D.hip_steps_fn(model, t, k, seed=seed, verify=verify and j == 0, guard=guard and j == len(segs) - 1)
+           for j, (t, k) in enumerate(segs)]
+    if len(fns) == 1:
+        return fns[0]
+
+    def fn(*args, **kw):
+        for f in fns:
+            x = f(*args, **kw)
+        fn.last = fns[-1].last
+        return x
+
+    fn.last = None
+    fn.wants_global = True
+    return fn
+
+
+DUMP_BYTES = 63 * 10 ** 6  # --dump-outputs: at most this much data in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(d, arrays):
+    """Save {name: [n, ...] float32 tensor} as d/<name>.npy; when the arrays hold more than DUMP_BYTES, a fixed seeded sample of
+    rows (the same rows of every array) is saved instead -> {name: what was saved}.  A directory made here gets a `.gitignore`
+    of its own, so that a dump inside the working tree leaves it clean."""
+    import numpy as np
+    if not os.path.isdir(d):
+        os.makedirs(d)
+        with open(os.path.join(d, ".gitignore"), "w") as f:
+            f.write("*\n")
+    n = min(a.shape[0] for a in arrays.values())
+    row_bytes = sum(a[0].numel() * 4 for a in arrays.values())
+    keep = None
+    if n * row_bytes > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // row_bytes, replace=False))
+    info = {}
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy()
+        if keep is not None:
+            a = a[keep]
+        np.save(os.path.join(d, name + ".npy"), a)
+        info[name] = {"shape": list(a.shape), "dtype": str(a.dtype),
+                      "rows": "all" if keep is None else f"{len(keep)} of {n} (seeded sample)"}
+    return info
+
+
 def kernel_launch_times(eng, x_l, xc_l, t_start, n_steps, lo):
     """Average launch duration (us) of the attention-layer and layer-tail launch sites over `n_steps` extra steps, by HIP event pairs around
     every launch of that site on the launch stream (egoego_profile_begin / _end): {"qkv": (us, launches), "fc_ln": (us, launches)}."""
@@ -219,14 +281,14 @@ def trained_like_line(args, cfg, dev, B, T, K, W):
         model.hip_engine(verify=True, job=(B, T, cfg.timesteps), conditions=(xs * (1 - cm) + cm * noise["cond"]).contiguous())
         t_pack = time.perf_counter() - t_pack
     S = cfg.timesteps
-    timed_fn = D.hip_steps_fn(model, S - 1 - W, K, seed=7, verify=False, guard=False)
-    D.sample_local(D.hip_steps_fn(model, S - 1, max(W, 1), seed=7), xs, cm, noise)
+    timed_fn = chain_steps_fn(model, S, W, K, seed=7, verify=False, guard=False)
+    D.sample_local(chain_steps_fn(model, S, 0, max(W, 1), seed=7), xs, cm, noise)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     D.sample_local(timed_fn, xs, cm, noise)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    guarded_fn = D.hip_steps_fn(model, S - 1 - W, K, seed=7)  # (the same steps with the checksum and the runtime guard's read-back, like a caller's chain)
+    guarded_fn = chain_steps_fn(model, S, W, K, seed=7)  # (the same steps with the checksum and the runtime guard's read-back, like a caller's chain)
     tg = time.perf_counter()
     D.sample_local(guarded_fn, xs, cm, noise)
     torch.cuda.synchronize()
@@ -235,7 +297,8 @@ def trained_like_line(args, cfg, dev, B, T, K, W):
     prec = int(model.hip_precision_used)
     x_l = noise["x_T"].contiguous().clone()
     xc_l = (xs * (1 - cm) + cm * noise["cond"]).contiguous()
-    kern = kernel_launch_times(eng, x_l, xc_l, S - 1 - W, min(K, 20), 0)
+    t_prof = chain_segments(S, W, 1)[0][0]
+    kern = kernel_launch_times(eng, x_l, xc_l, t_prof, min(K, 20, t_prof + 1), 0)
     traffic, traffic_src = load_traffic(B, T, prec, "any")
     dominant, other = roofline_objects(eng, prec, B, T, kern, 1e3 * el / K, traffic, traffic_src)
     probe = model.hip_precision_probe or {}
@@ -295,6 +358,9 @@ def main():
     ap.add_argument("--no-trained-like", action="store_true",
                     help="skip the extra `trained_like` object (N=1 only: the same timed region on the trained-like checkpoint, in what 'auto' picks for it)")
     ap.add_argument("--dump", default=None, help="rank 0 saves the gathered poses of the timed call here (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed call returned, the gathered poses, as DIR/poses.npy (float32; a fixed seeded sample of "
+                         "windows above 63 MB): the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -368,15 +434,16 @@ def main():
     lo, hi = D.shard_bounds(B, rank, world)
     S = cfg.timesteps
     K, W = args.steps, args.warmup
-    if K + W > S:
-        raise SystemExit(f"steps + warmup must not exceed the {S}-step chain")
+    if K < 1 or W < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     # warm-up: W untimed steps through the very path that is timed (packs the workspace, captures the step graph,
     # and runs the collective once so that RCCL's lazy communicator set-up is not in the timed region)
     # the timed call neither checksums the weights nor reads the runtime guard's monitors back (host round trips): the warm-up call
     # just before it does both (and agrees on ONE plan over the ranks, plan.py); the guard of the timed chain runs after t1
-    timed_fn = D.hip_steps_fn(model, S - 1 - W, K, seed=7, verify=False, guard=False)
-    D.sample_sharded(D.hip_steps_fn(model, S - 1, max(W, 1), seed=7), xs, cm, noise, force_collective=force_coll)
+    # (step i of the chain is timestep S - 1 - i; past t = 0 a range starts the chain again: chain_segments)
+    timed_fn = chain_steps_fn(model, S, W, K, seed=7, verify=False, guard=False)
+    D.sample_sharded(chain_steps_fn(model, S, 0, max(W, 1), seed=7), xs, cm, noise, force_collective=force_coll)
     prec = int(model.hip_precision_used)  # (under torch.distributed: what group rank 0 resolved)
     torch.cuda.synchronize()
     if dist:
@@ -404,10 +471,11 @@ def main():
     finite = bool(torch.isfinite(out).all().item()) and tuple(out.shape) == (B, T, cfg.d_feats)
     if args.dump and rank == 0:
         torch.save(out.cpu(), args.dump)
+    dumped = dump_outputs(args.dump_outputs, {"poses": out}) if args.dump_outputs and rank == 0 else None
 
     # the product path as a caller runs it — weights checksummed, plan agreed on, the runtime guard's read-back at the end of the chain —
     # timed next to the bare region (the headline's timed call does none of the three)
-    guarded_fn = D.hip_steps_fn(model, S - 1 - W, K, seed=7)
+    guarded_fn = chain_steps_fn(model, S, W, K, seed=7)
     torch.cuda.synchronize()
     tg = time.perf_counter()
     D.sample_local(guarded_fn, xs, cm, noise)
@@ -420,7 +488,8 @@ def main():
     guard_demoted = int(model.hip_precision_used) != prec
     x_l = noise["x_T"][lo:hi].contiguous().clone()
     xc_l = (xs[lo:hi] * (1 - cm[lo:hi]) + cm[lo:hi] * noise["cond"][lo:hi]).contiguous()
-    kern = kernel_launch_times(eng, x_l, xc_l, S - 1 - W, min(K, 20), lo)
+    t_prof = chain_segments(S, W, 1)[0][0]
+    kern = kernel_launch_times(eng, x_l, xc_l, t_prof, min(K, 20, t_prof + 1), lo)
     traffic, traffic_src = load_traffic(Bl, T, int(model.hip_precision_used), args.weights)
 
     if rank == 0:
@@ -454,7 +523,8 @@ def main():
             "weights": args.weights if train_info is None else {"kind": args.weights, **train_info},
             "data": "synthetic",
             "config": {"workload": f"BASELINE configs[2]: B={B} windows x T={T} frames x 198 feats split over {world} GPU(s) "
-                                   f"({Bl} windows on rank 0), 1000-step DDPM chain (steps {S - 1 - W}..{S - W - K} timed), in-kernel "
+                                   f"({Bl} windows on rank 0), 1000-step DDPM chain (steps "
+                                   f"{', '.join(f'{t}..{t - k + 1}' for t, k in chain_segments(S, W, K))} timed), in-kernel "
                                    f"Philox noise keyed by the global window index, {'synthetic seeded' if train_info is None else 'trained-like'} weights",
                        "global_windows": B, "windows_per_gpu": Bl, "window_len": T,
                        "parallelism": f"window-sharded x{world} (dist.sample_sharded), one all_gather of the poses inside the timed region",
@@ -472,6 +542,8 @@ def main():
             "roofline": dominant,
             "roofline_second_kernel": other,
         }
+        if dumped is not None:
+            out_json["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if world == 1 and not args.no_trained_like and args.weights == "synthetic" and args.precision == "auto":
             try:
                 out_json["trained_like"] = trained_like_line(args, cfg, dev, B, T, K, W)
