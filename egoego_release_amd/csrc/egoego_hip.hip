@@ -102,7 +102,9 @@ struct egoego_ctx {
     // profiling
     int prof_id;
     std::vector<hipEvent_t> prof_events;
-    const char* last_kernel[EGOEGO_K_COUNT];  // the kernel variant each launch site of a step last dispatched to (egoego_last_kernel_name)
+    // the kernel variant each launch site of a step last dispatched to (egoego_last_kernel_name): one string per distinct launch;
+    // a stage that runs inside another stage's kernel (fused attention, fused layer tails) records that kernel in its own slot too
+    const char* last_kernel[EGOEGO_K_COUNT];
 };
 
 static const int N_MODEL = 512;
@@ -735,10 +737,10 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
             // blocks, two per CU: 53.7 us per launch at B=256 against 51.8)
             GemmOperands go{c->w_embed, (size_t)N_MODEL * c->KE, w.xall, w.xall_plane, c->KE / 16, 1, rows / 128, row0 / 128 EG_DBG(, g_ablate, g_trace)};
             EpiEmbed<NP, 4, 128> e{c->b_embed, c->pe, c->tt_table, w.t_idx, embed_out, w.h_plane, g.Lr, g.T, g.B, w.hA8, w.h_plane, w.hA_scale, io.state, io.ts};
-            c->last_kernel[EGOEGO_K_EMBED] = "gemm_kernel:EpiEmbed";
+            c->last_kernel[EGOEGO_K_EMBED] = "gemm_kernel:EpiEmbed<CfgB>";
             if (int r = launch_gemm<CfgB<NP>>(go, e, s)) return r;
         } else {
-            c->last_kernel[EGOEGO_K_EMBED] = "gemm_kernel:EpiEmbed";
+            c->last_kernel[EGOEGO_K_EMBED] = "gemm_kernel:EpiEmbed<CfgA>";
             GemmOperands go{c->w_embed, (size_t)N_MODEL * c->KE, w.xall, w.xall_plane, c->KE / 16, N_MODEL / BLK_A_F, tb_a, t0_a EG_DBG(, g_ablate, g_trace)};
             EpiEmbed<NP> e{c->b_embed, c->pe, c->tt_table, w.t_idx, w.hA, w.h_plane, g.Lr, g.T, g.B, nullptr, 0, nullptr, io.state, io.ts};
             if (int r = launch_gemm<CfgA<NP>>(go, e, s)) return r;
@@ -790,28 +792,31 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
             if (w.att_img && nw * H * 6 <= ATTN_SPLIT6_MAX_BLOCKS) {  // ... six four-wave workgroups while each of those still gets a CU of its own
                 const AttnSplitBufs sb{w.att_img, w.sq8, w.sk8, (float*)w.V};
                 c->last_kernel[EGOEGO_K_QKV] = "attn_proj6_i8_kernel";
+                c->last_kernel[EGOEGO_K_ATTN] = "attn_core_s_kernel";
                 attn_proj6_i8_kernel<<<dim3(nw * H * 6), dim3(256), ATTN_PROJ6_SMEM, s>>>(al, sb);
                 HIP_TRY(hipGetLastError());
                 attn_core_s_kernel<<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
             } else if (w.att_img && nw * H * 3 <= ATTN_SPLIT_MAX_BLOCKS) {
                 const AttnSplitBufs sb{w.att_img, w.sq8, w.sk8, (float*)w.V};
                 c->last_kernel[EGOEGO_K_QKV] = "attn_proj_i8_kernel";
+                c->last_kernel[EGOEGO_K_ATTN] = "attn_core_s_kernel";
                 attn_proj_i8_kernel<<<dim3(nw * H * 3), dim3(512), ATTN_PROJ_SMEM, s>>>(al, sb);
                 HIP_TRY(hipGetLastError());
                 attn_core_s_kernel<<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
             } else if (w.att_img && nw * H * 2 <= ATTN_SPLIT2_MAX_BLOCKS) {
                 const AttnSplitBufs sb{w.att_img, w.sq8, w.sk8, (float*)w.V};
                 c->last_kernel[EGOEGO_K_QKV] = "attn_proj2_i8_kernel";
+                c->last_kernel[EGOEGO_K_ATTN] = "attn_core_s_kernel";
                 attn_proj2_i8_kernel<<<dim3(nw * H * 2), dim3(512), ATTN_PROJ_SMEM, s>>>(al, sb);
                 HIP_TRY(hipGetLastError());
                 attn_core_s_kernel<<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
             } else
             // up to 24 windows x 4 heads: two workgroups per (window, head), half the queries each (attn_layer_i8h.h)
             if (nw * H * 2 <= ATTN_HALF_MAX_BLOCKS) {
-                c->last_kernel[EGOEGO_K_QKV] = "attn_layer_i8h_kernel";
+                c->last_kernel[EGOEGO_K_QKV] = c->last_kernel[EGOEGO_K_ATTN] = "attn_layer_i8h_kernel";
                 attn_layer_i8h_kernel<<<dim3(nw * H * 2), dim3(512), AL_SMEM_BYTES, s>>>(al);
             } else {
-                c->last_kernel[EGOEGO_K_QKV] = "attn_layer_i8w_kernel";
+                c->last_kernel[EGOEGO_K_QKV] = c->last_kernel[EGOEGO_K_ATTN] = "attn_layer_i8w_kernel";
                 attn_layer_i8w_kernel<<<dim3(nw * H), dim3(512), AW_DYN_SMEM_BYTES, s>>>(al);
             }
             HIP_TRY(hipGetLastError());
@@ -826,7 +831,7 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
                 HIP_TRY(allow_smem(kern, smem));
                 once.done();
             }
-            c->last_kernel[EGOEGO_K_QKV] = "qkv_attn_kernel";
+            c->last_kernel[EGOEGO_K_QKV] = c->last_kernel[EGOEGO_K_ATTN] = "qkv_attn_kernel";
             kern<<<dim3(nw * H), dim3(CfgA<NP>::NT), smem, s>>>(go, eqk, ev, aa, H);
             HIP_TRY(hipGetLastError());
         } else {
@@ -939,6 +944,7 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
                 ta.stop = !last_dbg ? 0 : (io.stop_stage == EGOEGO_DBG_ATTN_LN ? 1 : (io.stop_stage == EGOEGO_DBG_FFN_HIDDEN ? 2 : 0));
                 EG_DBG(ta.trace = g_trace;)
                 if (int r = launch_tail(c, ta, rows, s, act8_only)) return r;
+                c->last_kernel[EGOEGO_K_FFN1] = c->last_kernel[EGOEGO_K_FFN2_LN] = c->last_kernel[EGOEGO_K_FC_LN];
                 if (last_dbg) return 0;
                 continue;
             }
@@ -964,7 +970,7 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
                 once.done();
             }
             const int stop = !last_dbg ? 0 : (io.stop_stage == EGOEGO_DBG_ATTN_LN ? 1 : (io.stop_stage == EGOEGO_DBG_FFN_HIDDEN ? 2 : 0));
-            c->last_kernel[EGOEGO_K_FC_LN] = "layer_tail_i8_kernel";
+            c->last_kernel[EGOEGO_K_FC_LN] = c->last_kernel[EGOEGO_K_FFN1] = c->last_kernel[EGOEGO_K_FFN2_LN] = "layer_tail_i8_kernel";
             kern<<<dim3(nb), dim3(CfgBs<NP>::NT), CfgBs<NP>::SMEM_BYTES + 6144, s>>>(g1, e1, g2, L.s_1, e2, g3, L.s_2, e3, stop);
             HIP_TRY(hipGetLastError());
             if (last_dbg) return 0;
@@ -1002,7 +1008,7 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
                     HIP_TRY(allow_smem(kern, CfgB<NP>::SMEM_BYTES));
                     once.done();
                 }
-                c->last_kernel[EGOEGO_K_FC_LN] = "layer_tail_kernel:128";
+                c->last_kernel[EGOEGO_K_FC_LN] = c->last_kernel[EGOEGO_K_FFN1] = c->last_kernel[EGOEGO_K_FFN2_LN] = "layer_tail_kernel:128";
                 kern<<<dim3(rows / 128), dim3(CfgB<NP>::NT), CfgB<NP>::SMEM_BYTES, s>>>(g1, f1, g2, e2, g3, f3);
                 HIP_TRY(hipGetLastError());
                 continue;
@@ -1013,7 +1019,7 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
                 HIP_TRY(allow_smem(kern, CfgBs<NP>::SMEM_BYTES));
                 once.done();
             }
-            c->last_kernel[EGOEGO_K_FC_LN] = "layer_tail_kernel";
+            c->last_kernel[EGOEGO_K_FC_LN] = c->last_kernel[EGOEGO_K_FFN1] = c->last_kernel[EGOEGO_K_FFN2_LN] = "layer_tail_kernel";
             kern<<<dim3(nb), dim3(CfgBs<NP>::NT), CfgBs<NP>::SMEM_BYTES, s>>>(g1, e1, g2, e2, g3, e3);
             HIP_TRY(hipGetLastError());
             continue;
@@ -1021,20 +1027,22 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
         // --- fc + residual + LayerNorm (+ padding mask) (TM:92-93, 135)
         {
             ProfScope ps(c, EGOEGO_K_FC_LN, s);
-            c->last_kernel[EGOEGO_K_FC_LN] = "gemm_kernel:EpiResLN";
             if (small_ln) {
                 GemmOperands go{L.w_fc, (size_t)N_MODEL * HD, w.O, w.o_plane, HD / 16, 1, rows / 64, row0 / 64 EG_DBG(, g_ablate, g_trace)};
                 if (go.ntb <= SMALL_GRID) {
                     GemmOperands gt{L.w_fc, (size_t)N_MODEL * HD, w.O, w.o_plane, HD / 16, 1, rows / 32, row0 / 32 EG_DBG(, g_ablate, g_trace)};
                     EpiResLN<NP, 4, 32> e{L.b_fc, w.hA, w.h_plane, L.ln1_g, L.ln1_b, io.row_mask, w.hB, w.h_plane, 1e-5f};
+                    c->last_kernel[EGOEGO_K_FC_LN] = "gemm_kernel:EpiResLN<CfgBt>";
                     if (int r = launch_gemm<CfgBt<NP>>(gt, e, s)) return r;
                 } else {
                     EpiResLN<NP, 4, 64> e{L.b_fc, w.hA, w.h_plane, L.ln1_g, L.ln1_b, io.row_mask, w.hB, w.h_plane, 1e-5f};
+                    c->last_kernel[EGOEGO_K_FC_LN] = "gemm_kernel:EpiResLN<CfgBs>";
                     if (int r = launch_gemm<CfgBs<NP>>(go, e, s)) return r;
                 }
             } else {
                 GemmOperands go{L.w_fc, (size_t)N_MODEL * HD, w.O, w.o_plane, HD / 16, 1, tb_b, t0_b EG_DBG(, g_ablate, g_trace)};
                 EpiResLN<NP, 4, 128> e{L.b_fc, w.hA, w.h_plane, L.ln1_g, L.ln1_b, io.row_mask, w.hB, w.h_plane, 1e-5f};
+                c->last_kernel[EGOEGO_K_FC_LN] = "gemm_kernel:EpiResLN<CfgB>";
                 if (int r = launch_gemm<CfgB<NP>>(go, e, s)) return r;
             }
         }
@@ -1046,8 +1054,12 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
             EpiTiled<true, NP> e{L.b_1, w.F, w.h_plane, N_MODEL / 16};
             if (go.nfb * go.ntb <= SMALL_GRID) {
                 go.nfb = N_MODEL / 128;
+                c->last_kernel[EGOEGO_K_FFN1] = "gemm_kernel:EpiTiled<CfgAh>";
                 if (int r = launch_gemm<CfgAh<NP>>(go, e, s)) return r;
-            } else if (int r = launch_gemm<CfgA<NP>>(go, e, s)) return r;
+            } else {
+                c->last_kernel[EGOEGO_K_FFN1] = "gemm_kernel:EpiTiled<CfgA>";
+                if (int r = launch_gemm<CfgA<NP>>(go, e, s)) return r;
+            }
         }
         if (last_dbg && io.stop_stage == EGOEGO_DBG_FFN_HIDDEN) return 0;
         // --- FFN conv 2 + residual + LayerNorm (+ padding mask) (TM:111-114, 139)
@@ -1059,16 +1071,19 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
                     GemmOperands gt{L.w_2, (size_t)N_MODEL * N_MODEL, w.F, w.h_plane, N_MODEL / 16, 1, rows / 32, row0 / 32 EG_DBG(, g_ablate, g_trace)};
                     EpiResLN<NP, 4, 32> e{L.b_2, w.hB, w.h_plane, L.ln2_g, L.ln2_b, io.row_mask, w.hA, w.h_plane, 1e-5f, q8p, w.h_plane, w.hA_scale};
                     e.outlier = om2; e.outlier_rows = g.Mvalid;
+                    c->last_kernel[EGOEGO_K_FFN2_LN] = "gemm_kernel:EpiResLN<CfgBt>";
                     if (int r = launch_gemm<CfgBt<NP>>(gt, e, s)) return r;
                 } else {
                     EpiResLN<NP, 4, 64> e{L.b_2, w.hB, w.h_plane, L.ln2_g, L.ln2_b, io.row_mask, w.hA, w.h_plane, 1e-5f, q8p, w.h_plane, w.hA_scale};
                     e.outlier = om2; e.outlier_rows = g.Mvalid;
+                    c->last_kernel[EGOEGO_K_FFN2_LN] = "gemm_kernel:EpiResLN<CfgBs>";
                     if (int r = launch_gemm<CfgBs<NP>>(go, e, s)) return r;
                 }
             } else {
                 GemmOperands go{L.w_2, (size_t)N_MODEL * N_MODEL, w.F, w.h_plane, N_MODEL / 16, 1, tb_b, t0_b EG_DBG(, g_ablate, g_trace)};
                 EpiResLN<NP, 4, 128> e{L.b_2, w.hB, w.h_plane, L.ln2_g, L.ln2_b, io.row_mask, w.hA, w.h_plane, 1e-5f, q8p, w.h_plane, w.hA_scale};
                     e.outlier = om2; e.outlier_rows = g.Mvalid;
+                c->last_kernel[EGOEGO_K_FFN2_LN] = "gemm_kernel:EpiResLN<CfgB>";
                 if (int r = launch_gemm<CfgB<NP>>(go, e, s)) return r;
             }
         }
@@ -1099,11 +1114,14 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
         } else {
             GemmOperands go{c->w_out, (size_t)c->NOUT * N_MODEL, w.hA, w.h_plane, N_MODEL / 16, 1, tb_c, t0_c EG_DBG(, g_ablate, g_trace)};
             EpiOut<NP> e{io.out};
-            c->last_kernel[EGOEGO_K_OUT] = "gemm_kernel:EpiOut";
             if (tb_c <= SMALL_GRID) {
                 GemmOperands gs{c->w_out, (size_t)c->NOUT * N_MODEL, w.hA, w.h_plane, N_MODEL / 16, 1, rows / 64, row0 / 64 EG_DBG(, g_ablate, g_trace)};
+                c->last_kernel[EGOEGO_K_OUT] = "gemm_kernel:EpiOut<CfgC2>";
                 if (int r = launch_gemm<CfgC2<NP>>(gs, e, s)) return r;
-            } else if (int r = launch_gemm<CfgC<NP>>(go, e, s)) return r;
+            } else {
+                c->last_kernel[EGOEGO_K_OUT] = "gemm_kernel:EpiOut<CfgC>";
+                if (int r = launch_gemm<CfgC<NP>>(go, e, s)) return r;
+            }
         }
     }
     return 0;
