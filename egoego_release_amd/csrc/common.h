@@ -221,7 +221,9 @@ struct StepState {
     int64_t window_offset; // global index of window 0 (shard-invariant noise)
     // Outlier monitor of the int8-slice precisions (egoego_outlier_stats): site 2 * layer + (0: LayerNorm-1, 1: LayerNorm-2) holds
     // the bit pattern of max |value| over every row that epilogue has quantised (one scale per row) since the last reset —
-    // positive floats order like their bit patterns, so the kernels use one atomicMax per workgroup.  Layers >= 8 are not recorded.
+    // positive floats order like their bit patterns, so the kernels use one atomicMax per workgroup.  A site whose LayerNorm writes
+    // no int8 rows in the running form stays 0 (which ones: include/egoego_hip.h).  Every row below B * Lr counts, each window's
+    // padding rows included (zero under a row mask); the rows that pad the call to whole blocks do not.  Layers >= 8 are not recorded.
     unsigned ln_max[16];
 };
 static constexpr int OUTLIER_SITES = 16;

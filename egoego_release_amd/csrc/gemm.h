@@ -888,7 +888,7 @@ struct EpiResLN {
     unsigned* outlier;
     float* outlier_park;  // ... or an LDS slot that receives the maximum instead (mid-kernel epilogues: an atomic in the vector-memory queue
                           // would sit in front of the next contraction's counted waits; the kernel flushes the slot at its end)
-    int outlier_rows;  // token tiles reaching beyond this row hold the padding of the last token block (uninitialised inputs): not recorded
+    int outlier_rows;  // rows from this one on hold the padding of the last token block (uninitialised inputs): not recorded
     // rr: the residual as int8 rows in registers (instead of res / res8); keep: receives the int8 rows this call produces
     template <int FT, int TT, class ResR = NoRows, class KeepR = NoRows>
     __device__ void run(f32x16 (&acc)[FT][TT], int f0, int t0, int lane, int wf, int wt, char* smem, const ResR* rr = nullptr,
@@ -1076,7 +1076,9 @@ struct EpiResLN {
                     float rmax = 0.f;
 #pragma unroll
                     for (int w = 0; w < NWF; ++w) rmax = fmaxf(rmax, red3[slot[j] + w * BT]);
-                    if (t0 + j * 32 + 32 <= outlier_rows) omax = fmaxf(omax, rmax);  // (wave-uniform: whole token tiles only)
+                    // row by row: a tile may straddle outlier_rows (windows of 208 rows: an odd batch ends mid-tile, and whole tiles
+                    // only would drop the last window's tokens 192..207)
+                    if (t0 + j * 32 + col < outlier_rows) omax = fmaxf(omax, rmax);
                 }
 #pragma unroll
                 for (int o = 16; o >= 1; o >>= 1) omax = fmaxf(omax, __shfl_xor(omax, o));

@@ -236,8 +236,16 @@ const char* egoego_last_kernel_name(const egoego_ctx* ctx, int kernel_id);
 
 /* Outlier monitor of the int8-slice precisions (8, 9).  Those keep ONE scale per activation row (16-bit fixed point): a row whose
  * largest entry is far above the rest costs every other entry of the row that many bits.  Every LayerNorm epilogue that
- * quantises its rows records the largest |value| it has seen (one atomicMax per workgroup into the workspace's step state; nothing
- * is recorded in precisions 3 / 1, for layers >= 8, or for the padding rows of the last token block).
+ * quantises its rows records the largest |value| it has seen (one atomicMax per workgroup into the workspace's step state).
+ * Only those record, so the sites a call fills depend on the form:
+ *   precision 8, and precision 9 at T + 1 <= 64 (it runs precision 8's kernels there): LayerNorm-1 of every layer, LayerNorm-2 of
+ *     every layer but the last (linear_out reads the last layer's split-bf16 rows);
+ *   precision 8 + EGOEGO_FLAG_FFN16: LayerNorm-2 of every layer but the last, no LayerNorm-1 (the FFN reads split-bf16 rows);
+ *   precision 9 at T + 1 >= 65, with EGOEGO_FLAG_FC24 or not: both LayerNorms of every layer;
+ *   precisions 3 / 1, and layers >= 8: nothing.
+ * Every row of the B windows is recorded: with a row mask each window's padding rows (T + 1 .. Lr - 1) are zero, without one they
+ * are recorded as computed.  Only the rows that pad the call to whole token blocks are not.  Weights packed from a mean-shifted
+ * state dict record the shifted rows (the LayerNorm output minus the per-feature shift).
  * host_out[2 * layer + k] (k = 0: self_attn.layer_norm, k = 1: pos_ffn.layer_norm; n_out <= 16 entries, 0 = nothing recorded)
  * receives the maxima accumulated by every call on this workspace since the last reset; reset != 0 clears them afterwards.
  * Divide by the rms of the LayerNorm's (gain, bias) to get the row's crest factor — what model.py's runtime guard compares
