@@ -4,12 +4,16 @@ Only the sampling hot path lives here: HIP kernels + C ABI in cs
 mirror of the reference's CondGaussianDiffusion interface in model.py.
 """
 from .synthetic import ModelConfig, make_weights, make_head_windows, head_condition_mask  # noqa: F401
+from .synthetic import Stage1Config, make_stage1_weights  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch.cuda or the .so
     if name in ("CondGaussianDiffusion", "TransformerDiffusionModel"):
         from . import model
         return getattr(model, name)
+    if name in ("HeadFormer", "HeadNormalFormer", "estimate_head_pose"):
+        from . import stage1
+        return getattr(stage1, name)
     if name == "HipEngine":
         from .engine import HipEngine
         return HipEngine

@@ -9,7 +9,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libegoego_hip.so")
 PERFDEBUG_LIB_PATH = os.path.join(os.path.dirname(_PKG), "tools", "_build", "libegoego_hip_perfdebug.so")  # tools/ only: `build --perfdebug`
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 FLAG_NO_GRAPH = 1
 FLAG_FC24 = 2  # precision 9 only: fc's weights as three int8 slices (include/egoego_hip.h)
 FLAG_FFN16 = 4  # precision 8 only: the FFN contractions on split-bf16 (int8 slices in the attention layer only)
@@ -46,10 +46,24 @@ class Schedule(C.Structure):
                                          "sqrt_recipm1_alphas_cumprod", "alphas_cumprod")]
 
 
+class S1Config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "d_feats", "d_model", "n_head", "n_dec_layers", "d_k", "d_v", "window")]
+
+
+class S1Weights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("start_conv_w", "start_conv_b", "position_vec")] + [
+        ("layers", C.POINTER(LayerWeights)), ("head_w", C.c_void_p * 8), ("head_b", C.c_void_p * 8)]
+
+
+S1_HEADNET, S1_GRAVITYNET = 0, 1
+
 EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoego_ctx_destroy",
            "egoego_load_weights", "egoego_load_schedule", "egoego_workspace_bytes", "egoego_denoise",
            "egoego_p_sample", "egoego_sample_loop", "egoego_ddim_loop", "egoego_rot6d_to_matrix", "egoego_convert_model_res", "egoego_window_prefix", "egoego_window_condition",
-           "egoego_profile_begin", "egoego_profile_end", "egoego_debug_stage", "egoego_last_kernel_name", "egoego_outlier_stats"]
+           "egoego_profile_begin", "egoego_profile_end", "egoego_debug_stage", "egoego_last_kernel_name", "egoego_outlier_stats",
+           "egoego_s1_last_error", "egoego_s1_ctx_create", "egoego_s1_ctx_destroy", "egoego_s1_load_weights",
+           "egoego_s1_workspace_bytes", "egoego_s1_encode", "egoego_s1_gravity_features", "egoego_s1_integrate",
+           "egoego_s1_gravity_apply"]
 OUTLIER_SITES = 16
 
 _lib = None
@@ -103,10 +117,26 @@ def load():
     lib.egoego_last_kernel_name.argtypes = [vp, i32]
     lib.egoego_last_kernel_name.restype = C.c_char_p
     lib.egoego_outlier_stats.argtypes = [vp, i32, i32, vp, sz, c_float_p, i32, i32, vp]
+    lib.egoego_s1_last_error.restype = C.c_char_p
+    lib.egoego_s1_ctx_create.argtypes = [C.POINTER(S1Config), i32, C.POINTER(vp)]
+    lib.egoego_s1_ctx_destroy.argtypes = [vp]
+    lib.egoego_s1_ctx_destroy.restype = None
+    lib.egoego_s1_load_weights.argtypes = [vp, C.POINTER(S1Weights), vp]
+    lib.egoego_s1_workspace_bytes.argtypes = [vp, i32]
+    lib.egoego_s1_workspace_bytes.restype = sz
+    lib.egoego_s1_encode.argtypes = [vp, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.egoego_s1_gravity_features.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.egoego_s1_integrate.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp]
+    lib.egoego_s1_gravity_apply.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def check_s1(rc):
+    if rc != 0:
+        raise EgoEgoHipError(f"libegoego_hip stage-1 error {rc}: {load().egoego_s1_last_error().decode()}")
 
 
 def check(rc):

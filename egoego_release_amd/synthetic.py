@@ -177,3 +177,61 @@ def make_motion_windows(B, T, seed=0, device="cpu", d_feats=198):
     hi = torch.tensor([1.5, 1.5, 2.0], device=dev)
     pos = ((pos - lo) / (hi - lo) * 2 - 1).clamp(-1, 1)
     return torch.cat((pos.reshape(B, T, 66), Rg[..., :2, :].reshape(B, T, 132)), -1).float()
+
+
+# ------------------------------------------------------------------------------------------ stage 1 (HeadNet / GravityNet)
+class Stage1Config:
+    """Shapes of a stage-1 estimator: HeadFormer (kind 'headnet', head_estimation_transformer.py:48-95) or HeadNormalFormer
+    (kind 'gravitynet', head_normal_estimation_transformer.py:65-110).  d_feats: 512 optical-flow features / 18 SLAM features."""
+
+    def __init__(self, kind, window, n_dec_layers, n_head=4, d_k=256, d_v=256, d_model=256):
+        if kind not in ("headnet", "gravitynet"):
+            raise ValueError(f"unknown stage-1 kind {kind!r}")
+        self.kind, self.window, self.n_dec_layers = kind, window, n_dec_layers
+        self.n_head, self.d_k, self.d_v, self.d_model = n_head, d_k, d_v, d_model
+        self.d_feats = 512 if kind == "headnet" else 18
+
+    def head_dims(self):
+        """{prefix: [(out, in), ...]} of the MLP heads (egoego/model/mlp.py) and their final Linear."""
+        dm = self.d_model
+        if self.kind == "headnet":
+            return {"action_va": [(1024, dm), (512, 1024), (256, 512), (3, 256)],
+                    "action_dist": [(1024, dm), (512, 1024), (256, 512), (1, 256)]}
+        return {"action_normal": [(512, dm), (256, 512), (3, 256)]}
+
+
+def make_stage1_weights(kind, cfg, seed=0):
+    """Seeded synthetic state dict of a stage-1 estimator, keyed like the reference module's (`kind`: 'headnet' |
+    'gravitynet'; cfg: Stage1Config or anything with window / n_dec_layers / n_head / d_k / d_v / d_model).  Init scales are
+    the reference's (transformer_module.py:44-55 and PyTorch's defaults); LayerNorm affines are perturbed like make_weights'."""
+    if not isinstance(cfg, Stage1Config):
+        cfg = Stage1Config(kind, cfg.window, cfg.n_dec_layers, cfg.n_head, cfg.d_k, cfg.d_v, cfg.d_model)
+    dm, H, dk, dv = cfg.d_model, cfg.n_head, cfg.d_k, cfg.d_v
+    sd = {}
+    tr = "action_transformer."
+
+    def lin(name, out_f, in_f, conv=False):
+        b = 1.0 / np.sqrt(in_f)
+        sd[name + ".weight"] = _uniform(seed, name + ".weight", (out_f, in_f, 1) if conv else (out_f, in_f), b)
+        sd[name + ".bias"] = _uniform(seed, name + ".bias", (out_f,), b)
+
+    lin(tr + "start_conv", dm, cfg.d_feats, conv=True)
+    sd[tr + "position_vec.weight"] = sinusoid_position_table(cfg.window + 1, dm)
+    for i in range(cfg.n_dec_layers):
+        a = tr + f"layer_stack.{i}.self_attn."
+        for nm, dd in (("w_q", dk), ("w_k", dk), ("w_v", dv)):
+            sd[a + nm + ".weight"] = _normal(seed, a + nm + ".weight", (H * dd, dm), np.sqrt(2.0 / (dm + dd)))
+            sd[a + nm + ".bias"] = _uniform(seed, a + nm + ".bias", (H * dd,), 1.0 / np.sqrt(dm))
+        sd[a + "fc.weight"] = _normal(seed, a + "fc.weight", (dm, H * dv), np.sqrt(2.0 / (dm + H * dv)))
+        sd[a + "fc.bias"] = _uniform(seed, a + "fc.bias", (dm,), 1.0 / np.sqrt(H * dv))
+        f = tr + f"layer_stack.{i}.pos_ffn."
+        lin(f + "w_1", dm, dm, conv=True)
+        lin(f + "w_2", dm, dm, conv=True)
+        for ln in (a + "layer_norm", f + "layer_norm"):
+            sd[ln + ".weight"] = 1.0 + _normal(seed, ln + ".weight", (dm,), 0.1)
+            sd[ln + ".bias"] = _normal(seed, ln + ".bias", (dm,), 0.1)
+    for prefix, dims in cfg.head_dims().items():
+        for j, (o, i_) in enumerate(dims[:-1]):
+            lin(f"{prefix}_mlp.affine_layers.{j}", o, i_)
+        lin(f"{prefix}_fc", *dims[-1])
+    return sd

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 6 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16 */
+#define EGOEGO_ABI_VERSION 7 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*) */
 
 enum {
     EGOEGO_OK = 0,
@@ -262,6 +262,79 @@ enum { EGOEGO_DBG_EMBED = 0, EGOEGO_DBG_Q = 1, EGOEGO_DBG_K = 2, EGOEGO_DBG_V = 
 int egoego_debug_stage(egoego_ctx* ctx, const float* d_x, const float* d_x_cond, const int64_t* d_t,
                        const float* d_row_mask, int layer, int stage, float* d_out, int B, int T,
                        void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ==================================================================================================================
+ * Stage 1: the head-pose estimators HeadNet (HeadFormer, egoego/model/head_estimation_transformer.py = HE) and GravityNet
+ * (HeadNormalFormer, egoego/model/head_normal_estimation_transformer.py = HN) with precomputed optical-flow features
+ * (input_of_feats).  Both are the TM Decoder at d_model 256 (use_full_attention=True) plus ReLU MLP heads; every contraction
+ * is split-bf16 (three bf16 MFMAs, fp32 accumulate).  A stage-1 context is separate from the stage-2 one; the conventions above
+ * (device pointers, caller's stream, return codes) hold, and egoego_s1_last_error() describes the last stage-1 failure.
+ *
+ * Windows: a call runs W independent windows of `window` tokens each.  d_feats is [W][window][d_feats] fp32 (tokens past
+ * valid[w] are ignored and read as zero rows, as the reference's zero padding); d_valid is int32 [W], 0..window (more counts as window).  A padded
+ * token is NOT masked as a key (TM:126-141): it only has its sublayer outputs zeroed.
+ * ================================================================================================================== */
+enum { EGOEGO_S1_HEADNET = 0, EGOEGO_S1_GRAVITYNET = 1 };
+
+typedef struct egoego_s1_ctx egoego_s1_ctx;
+
+typedef struct {
+    int32_t kind;          /* EGOEGO_S1_HEADNET | EGOEGO_S1_GRAVITYNET */
+    int32_t d_feats;       /* 512 (HeadNet) / 18 (GravityNet); 1..1024 accepted */
+    int32_t d_model;       /* 256 (only value supported) */
+    int32_t n_head;        /* n_head * d_k == n_head * d_v == 1024 (only value supported) */
+    int32_t n_dec_layers;  /* 1..8 */
+    int32_t d_k;
+    int32_t d_v;
+    int32_t window;        /* 1..128: tokens per window; the position table has window + 1 rows (TM:180-182) */
+} egoego_s1_config;
+
+/* fp32 device tensors in the reference layout.  layers: HOST array of n_dec_layers entries (egoego_layer_weights, with 256 in
+ * place of 512).  head_w / head_b: the MLP heads' nn.Linear tensors in order —
+ *   HeadNet:    action_va_mlp.affine_layers.0..2, action_va_fc, action_dist_mlp.affine_layers.0..2, action_dist_fc (8 entries);
+ *   GravityNet: action_normal_mlp.affine_layers.0..1, action_normal_fc (3 entries, the rest NULL). */
+typedef struct {
+    const float* start_conv_w; const float* start_conv_b;  /* (256, d_feats, 1), (256) */
+    const float* position_vec;                              /* (window + 1, 256) */
+    const egoego_layer_weights* layers;
+    const float* head_w[8];
+    const float* head_b[8];
+} egoego_s1_weights;
+
+const char* egoego_s1_last_error(void);
+int egoego_s1_ctx_create(const egoego_s1_config* cfg, int device, egoego_s1_ctx** out);
+void egoego_s1_ctx_destroy(egoego_s1_ctx* ctx);
+/* Packs the weights into split-bf16 fragment-tiled planes; synchronises `stream`. */
+int egoego_s1_load_weights(egoego_s1_ctx* ctx, const egoego_s1_weights* w, void* stream);
+/* Scratch bytes of a call over n_windows windows (0 if the shape is not accepted). */
+size_t egoego_s1_workspace_bytes(const egoego_s1_ctx* ctx, int n_windows);
+
+/* HE:123-170 / HN:118-155 for W windows in one launch per stage (embed, then per layer Q/K/V projection, attention, fused tail,
+ * then the heads).  HeadNet: d_out [W][window][4] = (va xyz, distance scalar) of every token (padded tokens included);
+ * GravityNet: d_out [W][3] = the floor normal from token 0.  d_layers (optional, NULL = none): the encoder output of every layer,
+ * [n_dec_layers][W][window][256]. */
+int egoego_s1_encode(egoego_s1_ctx* ctx, const float* d_feats, const int32_t* d_valid, int n_windows, float* d_out,
+                     float* d_layers, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* GravityNet's per-frame input (HN:118-145): d_rot [S][Lmax][3][3] and d_trans [S][Lmax][3] fp32 (the first len[s] frames of
+ * each sequence), d_len int32 [S] -> d_feats [S][window][18] (frames truncated to window + 1, zero padded) and d_valid int32 [S]
+ * = min(len, window + 1) - 1. */
+int egoego_s1_gravity_features(const float* d_rot, const float* d_trans, const int32_t* d_len, int S, int Lmax, int window,
+                               float* d_feats, int32_t* d_valid, void* stream);
+
+/* HeadNet's integration and SLAM rescale (HE:97-119, 180-212, 214-308), fp64, one thread per sequence.  Sequence s has T[s]
+ * frames in the consecutive windows win0[s].. of d_heads ([*][window][4], egoego_s1_encode's output); q0 [S][4] (w,x,y,z) is
+ * its first head rotation; d_slam [S][Lmax][3] its aligned SLAM translation of len[s] frames.  Outputs: d_quat [S][Qmax][4]
+ * (T[s] + 1 rotations, at most Qmax), d_trans [S][Lmax][3] (len[s] rescaled positions), d_scale [S] (pred_scale). */
+int egoego_s1_integrate(const float* d_heads, int window, const int32_t* d_T, const int32_t* d_win0, const double* d_q0,
+                        const double* d_slam, const int32_t* d_len, int S, int Lmax, int Qmax, float dist_scale,
+                        double* d_quat, double* d_trans, double* d_scale, void* stream);
+
+/* GravityNet's trajectory (HN:230-294 around the host's Rodrigues and Umeyama steps), fp64, one thread per sequence:
+ * a_0 = 0, a_i = a_{i-1} + scale[s] Rn[s] (p_i - p_{i-1});  d_pose [S][Lmax][7] = (Ralign[s] a_i + origin[s], quat(Ralign[s] Rn[s] R_i))
+ * with w >= 0.  d_rot / d_trans / d_len as for egoego_s1_gravity_features; Rn, Ralign [S][3][3], scale [S], origin [S][3]. */
+int egoego_s1_gravity_apply(const float* d_rot, const float* d_trans, const int32_t* d_len, int S, int Lmax, const double* d_Rn,
+                            const double* d_scale, const double* d_Ralign, const double* d_origin, double* d_pose, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,9 +5,9 @@ The counterpart, for the stage this repo accelerates, of the reference's drivers
     eval_stage2.py:58-222 (test_diffusion / full_body_gen_cond_head_pose_sliding_window on ground-truth head poses)
     run_egoego.py:55-192  (the same call on stage-1 head poses, then fk_smpl and the MPJPE of
                            kinpoly/scripts/eval_metrics_imu_rec.py:297-301)
-with the reference's `--diffusion_*` flags (eval_stage2.py:395-404).  Stage 1 (HeadNet / GravityNet / DROID-SLAM), the
-AMASS / ARES datasets, SMPL-H and the pretrained weights are not part of this repo: every asset is an
-input file, and without `--weight` the run uses the seeded synthetic weights.
+with the reference's `--diffusion_*` flags (eval_stage2.py:395-404).  Stage 1 (HeadNet / GravityNet on precomputed optical-flow
+features) is egoego_release_amd.stage1; DROID-SLAM, RAFT, the AMASS / ARES datasets, SMPL-H and the pretrained weights are not part
+of this repo: every asset is an input file, and without `--weight` the run uses the seeded synthetic weights.
 
     python tools/run_stage2_demo.py --head_pose head_qpos.npy --stats cano_min_max_mean_std_data_window_120.p \\
         --rest_offsets rest_offsets.npy [--weight model-10.pt] [--gt_jpos gt.npy] --diffusion_window 120 --out out.npz
