@@ -10,7 +10,10 @@ One "step" = one p_sample (denoiser forward + DDPM posterior update, in-kernel P
 the GLOBAL batch of B=256 windows of T=120 frames x 198 features with inputs resident in HBM.  With N GPUs
 the batch is split (egoego_release_amd.dist: contiguous window shards, no data-path collective; STRONG
 scaling) and one RCCL all_gather of the poses to every rank closes the timed region.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up (the precision probe of "auto"
+included), the warm-up, the timed steps, --dump / --dump-outputs and the line.  --full also runs what it leaves out: the runtime
+guard's read-back of the timed chain, the same steps with checksum and guard, per-kernel launch times and the roofline objects, the
+`trained_like` line (N=1, auto) and the CPU baseline (N=1) -- about a minute and a half more on one MI355X.
 
 Environment: EGOEGO_DIST_BACKEND=gloo lets several ranks share one GPU (tests on a 1-GPU box; default "nccl" = RCCL);
 EGOEGO_FORCE_COLLECTIVE=1 initialises the process group and runs the all_gather even with ONE rank, so that RCCL
@@ -354,9 +357,12 @@ def main():
                     help="skip the pack-time precision probe (profiling runs: its small-batch launches would mix into per-kernel averages); "
                          "needs an explicit --precision")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel of every step (no hipGraph replay)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the runtime guard's read-back of the timed chain (outlier_*), the "
+                         "steps with checksum and guard, per-kernel launch times (roofline*), trained_like and cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-trained-like", action="store_true",
-                    help="skip the extra `trained_like` object (N=1 only: the same timed region on the trained-like checkpoint, in what 'auto' picks for it)")
+                    help="with --full: skip the extra `trained_like` object (N=1 only: the same timed region on the trained-like checkpoint, in what 'auto' picks for it)")
     ap.add_argument("--dump", default=None, help="rank 0 saves the gathered poses of the timed call here (tests)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="rank 0 writes what the timed call returned, the gathered poses, as DIR/poses.npy (float32; a fixed seeded sample of "
@@ -462,7 +468,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    model._outlier_guard(*timed_fn.last, group=D._group_of(None))  # the timed chain's LayerNorm monitors (collective verdict), outside the timed region
+    if args.full:
+        model._outlier_guard(*timed_fn.last, group=D._group_of(None))  # the timed chain's LayerNorm monitors (collective verdict), outside the timed region
     gather_ms, sample_ms = 1e3 * (t2 - t1), 1e3 * (t1 - t0)
     if dist:
         tmax = torch.tensor([el, gather_ms, sample_ms], device=dev, dtype=torch.float64)
@@ -473,30 +480,30 @@ def main():
         torch.save(out.cpu(), args.dump)
     dumped = dump_outputs(args.dump_outputs, {"poses": out}) if args.dump_outputs and rank == 0 else None
 
-    # the product path as a caller runs it — weights checksummed, plan agreed on, the runtime guard's read-back at the end of the chain —
-    # timed next to the bare region (the headline's timed call does none of the three)
-    guarded_fn = chain_steps_fn(model, S, W, K, seed=7)
-    torch.cuda.synchronize()
-    tg = time.perf_counter()
-    D.sample_local(guarded_fn, xs, cm, noise)
-    torch.cuda.synchronize()
-    ms_step_guarded = 1e3 * (time.perf_counter() - tg) / K
-    # per-kernel launch durations (HIP events on the launch stream), measured AFTER the timed region on this rank's
-    # shard: a few extra steps per kernel with event pairs around every launch of that kernel
     Bl = hi - lo
-    eng = model.hip_engine()  # (the runtime outlier guard may have re-packed in another precision after the timed call)
-    guard_demoted = int(model.hip_precision_used) != prec
-    x_l = noise["x_T"][lo:hi].contiguous().clone()
-    xc_l = (xs[lo:hi] * (1 - cm[lo:hi]) + cm[lo:hi] * noise["cond"][lo:hi]).contiguous()
-    t_prof = chain_segments(S, W, 1)[0][0]
-    kern = kernel_launch_times(eng, x_l, xc_l, t_prof, min(K, 20, t_prof + 1), lo)
-    traffic, traffic_src = load_traffic(Bl, T, int(model.hip_precision_used), args.weights)
+    if args.full:
+        # the product path as a caller runs it — weights checksummed, plan agreed on, the runtime guard's read-back at the end of the chain —
+        # timed next to the bare region (the headline's timed call does none of the three)
+        guarded_fn = chain_steps_fn(model, S, W, K, seed=7)
+        torch.cuda.synchronize()
+        tg = time.perf_counter()
+        D.sample_local(guarded_fn, xs, cm, noise)
+        torch.cuda.synchronize()
+        ms_step_guarded = 1e3 * (time.perf_counter() - tg) / K
+        # per-kernel launch durations (HIP events on the launch stream), measured AFTER the timed region on this rank's
+        # shard: a few extra steps per kernel with event pairs around every launch of that kernel
+        eng = model.hip_engine()  # (the runtime outlier guard may have re-packed in another precision after the timed call)
+        guard_demoted = int(model.hip_precision_used) != prec
+        x_l = noise["x_T"][lo:hi].contiguous().clone()
+        xc_l = (xs[lo:hi] * (1 - cm[lo:hi]) + cm[lo:hi] * noise["cond"][lo:hi]).contiguous()
+        t_prof = chain_segments(S, W, 1)[0][0]
+        kern = kernel_launch_times(eng, x_l, xc_l, t_prof, min(K, 20, t_prof + 1), lo)
+        traffic, traffic_src = load_traffic(Bl, T, int(model.hip_precision_used), args.weights)
 
     if rank == 0:
         steps_per_s = K / el
         fl_step = flops_per_window_step(T) * B
         ms_step = 1e3 * el / K
-        dominant, other = roofline_objects(eng, int(model.hip_precision_used), Bl, T, kern, ms_step, traffic, traffic_src)
         probe = model.hip_precision_probe
         out_json = {
             "metric": f"diffusion-steps/sec (B={B}, T={T}, 22-joint)",
@@ -506,9 +513,6 @@ def main():
             "steps": K,
             "warmup": W,
             "ms_per_step": ms_step,
-            # the same K steps as a caller's chain runs them (weights checksummed, plan agreed on, the runtime guard's LayerNorm monitors read
-            # back at the end): `value` times the bare region (those three run in the warm-up call before it / after t1)
-            "ms_per_step_with_checksum_and_guard": ms_step_guarded,
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -537,24 +541,31 @@ def main():
             "collective_backend": (backend if dist else None),
             "gather_ms": gather_ms if dist else None,
             "sample_ms": sample_ms,
-            "outlier_row_max": model.hip_outlier_seen,
-            "outlier_guard_demoted_after_timed_call": guard_demoted,
-            "roofline": dominant,
-            "roofline_second_kernel": other,
         }
         if dumped is not None:
             out_json["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
-        if world == 1 and not args.no_trained_like and args.weights == "synthetic" and args.precision == "auto":
-            try:
-                out_json["trained_like"] = trained_like_line(args, cfg, dev, B, T, K, W)
-            except Exception as e:  # the headline stands on its own
-                out_json["trained_like"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
-            try:
-                out_json["cpu_baseline"] = cpu_baseline(cfg, sd, B, T)
-                out_json["speedup_vs_cpu_baseline"] = steps_per_s / out_json["cpu_baseline"]["value"]
-            except Exception as e:  # the GPU number stands on its own
-                out_json["cpu_baseline"] = {"error": repr(e)}
+        if args.full:
+            dominant, other = roofline_objects(eng, int(model.hip_precision_used), Bl, T, kern, ms_step, traffic, traffic_src)
+            out_json.update({
+                # the same K steps as a caller's chain runs them (weights checksummed, plan agreed on, the runtime guard's LayerNorm monitors read
+                # back at the end): `value` times the bare region (those three run in the warm-up call before it / after t1)
+                "ms_per_step_with_checksum_and_guard": ms_step_guarded,
+                "outlier_row_max": model.hip_outlier_seen,
+                "outlier_guard_demoted_after_timed_call": guard_demoted,
+                "roofline": dominant,
+                "roofline_second_kernel": other,
+            })
+            if world == 1 and not args.no_trained_like and args.weights == "synthetic" and args.precision == "auto":
+                try:
+                    out_json["trained_like"] = trained_like_line(args, cfg, dev, B, T, K, W)
+                except Exception as e:  # the headline stands on its own
+                    out_json["trained_like"] = {"error": repr(e)}
+            if not args.no_cpu_baseline and world == 1:
+                try:
+                    out_json["cpu_baseline"] = cpu_baseline(cfg, sd, B, T)
+                    out_json["speedup_vs_cpu_baseline"] = steps_per_s / out_json["cpu_baseline"]["value"]
+                except Exception as e:  # the GPU number stands on its own
+                    out_json["cpu_baseline"] = {"error": repr(e)}
         print(json.dumps(out_json), flush=True)
     if dist:
         dist.destroy_process_group()

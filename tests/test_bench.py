@@ -1,4 +1,4 @@
-"""bench.py's step ranges (--steps / --warmup past the end of the chain) and --dump-outputs."""
+"""bench.py's step ranges (--steps / --warmup past the end of the chain), --dump-outputs and what --full adds to a plain run."""
 import json
 import os
 import subprocess
@@ -68,3 +68,23 @@ def test_bench_times_steps_past_the_chain_and_dumps_the_same_outputs_every_run(t
     assert got.dtype == np.float32 and np.array_equal(got, torch.load(tmp_path / "a.pt").numpy())
     _bench(common + ["--dump-outputs", str(tmp_path / "b")])
     assert np.array_equal(np.load(tmp_path / "b" / "poses.npy"), got)
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_out_what_full_measures_and_both_time_the_same_steps(tmp_path):
+    """A plain run prints the headline and what it is computed from, and nothing that takes runs of its own: no guarded steps, no
+    per-kernel launch times, no trained-like checkpoint, no CPU baseline.  --full adds them (trained_like and cpu_baseline are left out
+    here by their own flags) after the same timed call: the same configuration, precision and poses."""
+    common = ["--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", "8"]
+    plain = _bench(common + ["--dump-outputs", str(tmp_path / "plain")])
+    full = _bench(common + ["--full", "--no-cpu-baseline", "--no-trained-like", "--dump-outputs", str(tmp_path / "full")])
+    extra = {"ms_per_step_with_checksum_and_guard", "outlier_row_max", "outlier_guard_demoted_after_timed_call", "roofline",
+             "roofline_second_kernel"}
+    assert not (extra | {"trained_like", "cpu_baseline", "speedup_vs_cpu_baseline"}) & set(plain)
+    assert plain["ms_per_step"] > 0 and plain["output_finite"] and plain["value"] == pytest.approx(1e3 / plain["ms_per_step"])
+    assert extra <= set(full) and "trained_like" not in full and "cpu_baseline" not in full
+    assert full["ms_per_step_with_checksum_and_guard"] > 0 and full["roofline"]["launches"] > 0
+    assert full["roofline_second_kernel"]["launches"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "precision", "steps", "warmup", "config"):
+        assert plain[k] == full[k], k
+    assert np.array_equal(np.load(tmp_path / "plain" / "poses.npy"), np.load(tmp_path / "full" / "poses.npy"))
