@@ -5,13 +5,14 @@ mirror of the reference's CondGaussianDiffusion interface in model.py.
 """
 from .synthetic import ModelConfig, make_weights, make_head_windows, head_condition_mask  # noqa: F401
 from .synthetic import Stage1Config, make_stage1_weights  # noqa: F401
+from .synthetic import make_flow_cnn_weights, make_flows  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch.cuda or the .so
     if name in ("CondGaussianDiffusion", "TransformerDiffusionModel"):
         from . import model
         return getattr(model, name)
-    if name in ("HeadFormer", "HeadNormalFormer", "estimate_head_pose"):
+    if name in ("HeadFormer", "HeadNormalFormer", "estimate_head_pose", "FlowFeatureExtractor", "split_headnet_state_dict"):
         from . import stage1
         return getattr(stage1, name)
     if name == "HipEngine":

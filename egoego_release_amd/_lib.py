@@ -9,7 +9,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libegoego_hip.so")
 PERFDEBUG_LIB_PATH = os.path.join(os.path.dirname(_PKG), "tools", "_build", "libegoego_hip_perfdebug.so")  # tools/ only: `build --perfdebug`
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 FLAG_NO_GRAPH = 1
 FLAG_FC24 = 2  # precision 9 only: fc's weights as three int8 slices (include/egoego_hip.h)
 FLAG_FFN16 = 4  # precision 8 only: the FFN contractions on split-bf16 (int8 slices in the attention layer only)
@@ -56,6 +56,12 @@ class S1Weights(C.Structure):
 
 
 S1_HEADNET, S1_GRAVITYNET = 0, 1
+FLOW_N_CONV = 20
+
+
+class FlowWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p * FLOW_N_CONV) for n in ("conv_w", "bn_w", "bn_b", "bn_mean", "bn_var")] + [
+        ("fc_w", C.c_void_p), ("fc_b", C.c_void_p)]
 
 EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoego_ctx_destroy",
            "egoego_load_weights", "egoego_load_schedule", "egoego_workspace_bytes", "egoego_denoise",
@@ -63,7 +69,8 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_profile_begin", "egoego_profile_end", "egoego_debug_stage", "egoego_last_kernel_name", "egoego_outlier_stats",
            "egoego_s1_last_error", "egoego_s1_ctx_create", "egoego_s1_ctx_destroy", "egoego_s1_load_weights",
            "egoego_s1_workspace_bytes", "egoego_s1_encode", "egoego_s1_gravity_features", "egoego_s1_integrate",
-           "egoego_s1_gravity_apply"]
+           "egoego_s1_gravity_apply", "egoego_flow_last_error", "egoego_flow_ctx_create", "egoego_flow_ctx_destroy",
+           "egoego_flow_load_weights", "egoego_flow_workspace_bytes", "egoego_flow_features"]
 OUTLIER_SITES = 16
 
 _lib = None
@@ -128,6 +135,14 @@ def load():
     lib.egoego_s1_gravity_features.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.egoego_s1_integrate.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp]
     lib.egoego_s1_gravity_apply.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.egoego_flow_last_error.restype = C.c_char_p
+    lib.egoego_flow_ctx_create.argtypes = [i32, i32, C.POINTER(vp)]
+    lib.egoego_flow_ctx_destroy.argtypes = [vp]
+    lib.egoego_flow_ctx_destroy.restype = None
+    lib.egoego_flow_load_weights.argtypes = [vp, C.POINTER(FlowWeights), vp]
+    lib.egoego_flow_workspace_bytes.argtypes = [vp, i32]
+    lib.egoego_flow_workspace_bytes.restype = sz
+    lib.egoego_flow_features.argtypes = [vp, vp, i32, vp, vp, vp, sz, vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -137,6 +152,11 @@ def load():
 def check_s1(rc):
     if rc != 0:
         raise EgoEgoHipError(f"libegoego_hip stage-1 error {rc}: {load().egoego_s1_last_error().decode()}")
+
+
+def check_flow(rc):
+    if rc != 0:
+        raise EgoEgoHipError(f"libegoego_hip flow-CNN error {rc}: {load().egoego_flow_last_error().decode()}")
 
 
 def check(rc):

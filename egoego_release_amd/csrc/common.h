@@ -61,6 +61,14 @@ EG_D void split8(const float v[8], u32x4& hi, u32x4& lo) {
     lo = __builtin_bit_cast(u32x4, l);
 }
 
+// One split-bf16 product step: hi*hi + lo*hi + hi*lo as three v_mfma_f32_32x32x16_bf16 into one fp32 accumulator.
+EG_D f32x16 mfma3(u32x4 ah, u32x4 al, u32x4 bh, u32x4 bl, f32x16 c) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bh), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al), __builtin_bit_cast(bf16x8, bh), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bl), c, 0, 0, 0);
+    return c;
+}
+
 EG_D void unpack8(u32x4 hi, u32x4 lo, float v[8]) {
     bf16x8 h = __builtin_bit_cast(bf16x8, hi);
     bf16x8 l = __builtin_bit_cast(bf16x8, lo);

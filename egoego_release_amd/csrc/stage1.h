@@ -29,13 +29,6 @@ struct Lin {
     int N, K16;
 };
 
-EG_D f32x16 mfma3(u32x4 ah, u32x4 al, u32x4 bh, u32x4 bl, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bh), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al), __builtin_bit_cast(bf16x8, bh), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bl), c, 0, 0, 0);
-    return c;
-}
-
 // 8 consecutive fp32 of row `p` from column k (zero when !ok; columns >= K zero when !VEC).
 template <bool VEC>
 EG_D void load8(const float* p, int k, int K, bool ok, float v[8]) {

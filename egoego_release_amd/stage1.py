@@ -3,6 +3,7 @@ features, the ARES demo loader, and the assembly of the head pose that stage 2 c
 
 Reference files (paths relative to the reference root):
     HE = egoego/model/head_estimation_transformer.py         (HeadFormer)
+    RN = egoego/model/resnet.py                              (ResNet, FeatureExtractor)
     HN = egoego/model/head_normal_estimation_transformer.py  (HeadNormalFormer)
     TM = egoego/model/transformer_module.py                  (Decoder)
     AD = egoego/data/ares_demo_dataset.py                    (ARESDemoDataset)
@@ -12,6 +13,8 @@ Every per-token and per-frame step runs in libegoego_hip (egoego_s1_*): the deco
 GravityNet input features, the angular-velocity integration with the SLAM rescale, and GravityNet's trajectory.  The host keeps
 what the reference itself does in numpy on 3 x 3 matrices: the rotation from the predicted floor normal (Rodrigues, HN:47-63) and
 the Umeyama alignment (evo's PoseTrajectory3D.align).  torch is plumbing only; there is no fallback.
+
+FlowFeatureExtractor turns raw optical flow into those features (RN's ResNet-18, egoego_flow_* in libegoego_hip).
 """
 import ctypes as C
 import os
@@ -22,7 +25,7 @@ import torch
 from torch import nn
 
 from . import _lib, rotations
-from .synthetic import Stage1Config, make_stage1_weights
+from .synthetic import FLOW_FEATS, FLOW_IMG, Stage1Config, flow_cnn_convs, make_flow_cnn_weights, make_stage1_weights
 
 MAX_WINDOW = 128
 
@@ -44,8 +47,9 @@ def gravity_valid_frames(L, window):
 
 def _check_cfg(cfg, input_of_feats=True):
     if not input_of_feats:
-        raise NotImplementedError("stage 1 runs on precomputed optical-flow features only (input_of_feats): the ResNet-18 "
-                                  "optical-flow CNN is not implemented")
+        raise NotImplementedError("HeadFormer runs on precomputed optical-flow features only (input_of_feats): the ResNet-18 "
+                                  "optical-flow CNN is not implemented inside it; extract the features first with "
+                                  "FlowFeatureExtractor (split a checkpoint with split_headnet_state_dict)")
     if cfg.d_model != 256:
         raise ValueError(f"stage-1 d_model {cfg.d_model}: only 256 is supported")
     if cfg.n_head * cfg.d_k != 1024 or cfg.n_head * cfg.d_v != 1024 or cfg.n_head != 4:
@@ -306,6 +310,222 @@ class HeadFormer(_Stage1Module):
         return out
 
 
+# ------------------------------------------------------------------------------------------ the optical-flow CNN (RN)
+class FlowCNNEngine:
+    """One flow-CNN context of libegoego_hip on one GPU; frames run in chunks of `chunk_frames` (0 = the library's default)."""
+
+    N_STAGES = 5
+    STAGE_SHAPES = [(56, 56, 64), (56, 56, 64), (28, 28, 128), (14, 14, 256), (7, 7, 512)]
+
+    def __init__(self, device, chunk_frames=0):
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.EgoEgoHipError("the flow CNN needs a cuda (ROCm) device; there is no CPU path")
+        self.dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", self.dev_index)
+        self.chunk_frames = int(chunk_frames)
+        self._ctx = C.c_void_p()
+        _lib.check_flow(self.lib.egoego_flow_ctx_create(self.dev_index, self.chunk_frames, C.byref(self._ctx)))
+        self._ws = None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.dev_index).cuda_stream)
+
+    def load(self, sd, prefix="cnn.resnet."):
+        keep = []
+
+        def p(name):
+            t = sd[prefix + name].detach().to(device=self.device, dtype=torch.float32).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        w = _lib.FlowWeights()
+        for i, (conv, bn, *_) in enumerate(flow_cnn_convs()):
+            w.conv_w[i] = p(conv + ".weight")
+            w.bn_w[i], w.bn_b[i] = p(bn + ".weight"), p(bn + ".bias")
+            w.bn_mean[i], w.bn_var[i] = p(bn + ".running_mean"), p(bn + ".running_var")
+        w.fc_w, w.fc_b = p("fc.weight"), p("fc.bias")
+        with torch.cuda.device(self.dev_index):
+            _lib.check_flow(self.lib.egoego_flow_load_weights(self._ctx, C.byref(w), self._stream()))
+        del keep
+
+    def _workspace(self, N):
+        n = self.lib.egoego_flow_workspace_bytes(self._ctx, N)
+        if n == 0:
+            raise _lib.EgoEgoHipError(self.lib.egoego_flow_last_error().decode())
+        if self._ws is None or self._ws.numel() < n + 256:
+            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+        off = (-self._ws.data_ptr()) % 256
+        return self._ws.data_ptr() + off, self._ws.numel() - off
+
+    def features(self, flow, stages=False):
+        """flow [N, 224, 224, 2] fp32 -> [N, 512] (+ the five stage activations, NHWC, when `stages`)."""
+        flow = flow.to(self.device, torch.float32).contiguous()
+        N = flow.shape[0]
+        out = torch.empty(N, FLOW_FEATS, device=self.device)
+        dbg = None
+        if stages:
+            dbg = torch.empty(N * sum(h * w * c for h, w, c in self.STAGE_SHAPES), device=self.device)
+        ws, n = self._workspace(N)
+        with torch.cuda.device(self.dev_index):
+            _lib.check_flow(self.lib.egoego_flow_features(self._ctx, flow.data_ptr(), N, out.data_ptr(),
+                                                          dbg.data_ptr() if dbg is not None else None, ws, n, self._stream()))
+        if not stages:
+            return out
+        st, o = [], 0
+        for h, w, c in self.STAGE_SHAPES:
+            st.append(dbg[o:o + N * h * w * c].view(N, h, w, c))
+            o += N * h * w * c
+        return out, st
+
+    def close(self):
+        if getattr(self, "_ctx", None) and self._ctx.value:
+            self.lib.egoego_flow_ctx_destroy(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _BasicBlock(nn.Module):
+    def __init__(self, cin, cout, stride):
+        super().__init__()
+        self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(cout)
+        self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout)
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+
+
+class _ResNet18(nn.Module):
+    """torchvision's resnet18 parameters and buffers under its names, fc = Linear(512, 512) (RN:5-23); torchvision itself is
+    not needed."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        cin = 64
+        for li in range(1, 5):
+            cout = 64 << (li - 1)
+            setattr(self, f"layer{li}", nn.Sequential(_BasicBlock(cin, cout, 1 if li == 1 else 2), _BasicBlock(cout, cout, 1)))
+            cin = cout
+        self.fc = nn.Linear(512, FLOW_FEATS)
+
+
+class _ResNet(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.resnet = _ResNet18()
+
+
+class FlowFeatureExtractor(nn.Module):
+    """Drop-in for RN FeatureExtractor (lines 25-50) in eval mode: data['of'] [B, T, 224, 224, 2] -> [B, T, 512], on
+    libegoego_hip (split-bf16 implicit-GEMM convolutions, BatchNorm with the running statistics).
+
+    The reference builds its CNN from ImageNet weights (pretrained=True), which cannot be fetched here: this module starts from
+    the seeded synthetic weights of make_flow_cnn_weights(seed); load a checkpoint's state dict (122 keys cnn.resnet.*, e.g.
+    the first half of split_headnet_state_dict) to replace them, or pass it as `state_dict`, which skips the synthetic weights'
+    calibration pass.  The module starts in eval mode.  Training mode would
+    normalise with batch statistics, which is not implemented: forward() and extract() raise in train().  `chunk_frames` bounds
+    the frames per pass through the workspace (0 = the library's default, 256)."""
+
+    def __init__(self, device=None, chunk_frames=0, seed=0, state_dict=None):
+        super().__init__()
+        self.cnn_fdim = FLOW_FEATS
+        self.cnn = _ResNet()
+        with torch.no_grad():  # a given state dict skips drawing (and calibrating) the synthetic weights
+            self.load_state_dict(state_dict if state_dict is not None else make_flow_cnn_weights(seed))
+        for prm in self.cnn.parameters():
+            prm.requires_grad = False
+        self.device = torch.device(device) if device is not None else torch.device("cuda")
+        self.chunk_frames = int(chunk_frames)
+        self._engine = None
+        self._packed = None
+        self.eval()
+
+    def to(self, *args, **kwargs):
+        """RN:33-36: moves the parameters like nn.Module.to and remembers the device the features are computed on (any form
+        of the call: positional or keyword device, tensor, dtype only).  A CPU device makes extract() raise: there is no CPU
+        path."""
+        device = torch._C._nn._parse_to(*args, **kwargs)[0]
+        if device is not None:
+            self.device = torch.device(device)
+        super().to(*args, **kwargs)
+        return self
+
+    def cuda(self, device=None):
+        super().cuda(device)
+        if isinstance(device, torch.device):
+            self.device = device
+        else:
+            self.device = torch.device("cuda", device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        return self
+
+    def cpu(self):
+        super().cpu()
+        self.device = torch.device("cpu")
+        return self
+
+    def _params_version(self):  # (not `_version`: nn.Module stores its state-dict format version under that name)
+        return tuple((p.data_ptr(), p._version) for p in self.state_dict().values())
+
+    def engine(self):
+        dev = self.device
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        e = self._engine
+        if e is None or e.device != dev or e.chunk_frames != self.chunk_frames:
+            self._engine = FlowCNNEngine(dev, self.chunk_frames)
+            self._packed = None
+        v = self._params_version()
+        if v != self._packed:
+            self._engine.load(self.state_dict())
+            self._packed = v
+        return self._engine
+
+    def _check(self, flow):
+        if self.training:
+            raise RuntimeError("FlowFeatureExtractor runs BatchNorm with its running statistics only (eval mode): call .eval() "
+                               "first; training-mode batch statistics are not implemented")
+        if tuple(flow.shape[-3:]) != (FLOW_IMG, FLOW_IMG, 2):
+            raise ValueError(f"optical flow {tuple(flow.shape)}: [..., 224, 224, 2] expected (the reference hard-codes 224 x 224)")
+
+    def extract(self, flow, stages=False):
+        """flow [N, 224, 224, 2] (pixels, x and y) -> features [N, 512] fp32 on the module's device.  With `stages`, also the
+        activations after the stem and after layer1..4 as NHWC tensors (debugging)."""
+        flow = torch.as_tensor(flow)
+        self._check(flow)
+        if flow.dim() != 4:
+            raise ValueError(f"optical flow {tuple(flow.shape)}: [N, 224, 224, 2] expected")
+        if flow.shape[0] == 0:
+            out = torch.empty(0, FLOW_FEATS, device=self.engine().device)
+            return (out, []) if stages else out
+        return self.engine().features(flow, stages)
+
+    def forward(self, data):
+        """RN:38-50: data['of'] [B, T, 224, 224, 2] -> [B, T, 512]."""
+        of = torch.as_tensor(data["of"])
+        self._check(of)
+        if of.dim() != 5:
+            raise ValueError(f"data['of'] {tuple(of.shape)}: [B, T, 224, 224, 2] expected")
+        B, T = of.shape[:2]
+        return self.extract(of.reshape(B * T, FLOW_IMG, FLOW_IMG, 2)).reshape(B, T, self.cnn_fdim)
+
+
+def split_headnet_state_dict(sd):
+    """A HeadFormer state dict saved with input_of_feats off holds its CNN as cnn.resnet.* (HE:66-72), the names of RN
+    FeatureExtractor: -> (cnn_sd for FlowFeatureExtractor, the rest for HeadFormer(input_of_feats=True))."""
+    cnn = {k: v for k, v in sd.items() if k.startswith("cnn.")}
+    rest = {k: v for k, v in sd.items() if not k.startswith("cnn.")}
+    return cnn, rest
+
+
 def rotation_from_floor_normal(n):
     """HN:47-63 (numpy, float64): the rotation that takes the normal n onto +z (Rodrigues)."""
     a = np.asarray(n, np.float64).reshape(3)
@@ -460,6 +680,9 @@ def load_slam_res_and_align_first(npy_path, gt_head_pose):
     return atrans, arot.numpy(), aquat
 
 
+ARES_SRC_ROOT = "/viscam/u/jiamanli/datasets/egomotion_syn_dataset/habitat_rendering_replica_all"  # AD:101, of_files' root
+
+
 def load_ares_demo(data_root_folder):
     """ARESDemoDataset(data_root_folder) as a list of batches of one sequence (what its DataLoader with batch_size=1 yields:
     tensors with a leading batch axis): head_pose [1, T'+1, 7], head_vels [1, T', 6], of [1, T', 512], seq_len, seq_name, and the
@@ -476,7 +699,7 @@ def load_ares_demo(data_root_folder):
         q = {"head_pose": item["head_qpos"][:T + 1], "head_vels": head_vels[:T], "seq_len": T, "seq_name": item["seq_name"]}
         ofs = []
         for f in item["of_files"][:T]:
-            f = f.replace("/viscam/u/jiamanli/datasets/egomotion_syn_dataset/habitat_rendering_replica_all", data_root_folder)
+            f = f.replace(ARES_SRC_ROOT, data_root_folder)
             ofs.append(np.load(f.replace("raft_flows", "raft_of_feats")))
         q["of"] = np.stack(ofs)
         if os.path.exists(npy):

@@ -235,3 +235,94 @@ def make_stage1_weights(kind, cfg, seed=0):
             lin(f"{prefix}_mlp.affine_layers.{j}", o, i_)
         lin(f"{prefix}_fc", *dims[-1])
     return sd
+
+
+# ------------------------------------------------------------------------------------------ stage 1's optical-flow CNN (ResNet-18)
+FLOW_IMG = 224
+FLOW_FEATS = 512
+
+
+def flow_cnn_convs():
+    """The 20 convolutions of torchvision's resnet18 in the order of the C ABI (egoego_flow_weights):
+    [(conv name, BatchNorm name, c_in, c_out, kernel, stride, padding)] under the state-dict prefix of ResNet.resnet."""
+    out = [("conv1", "bn1", 3, 64, 7, 2, 3)]
+    cin = 64
+    for li in range(1, 5):
+        cout = 64 << (li - 1)
+        for b in range(2):
+            p = f"layer{li}.{b}."
+            s = 2 if li > 1 and b == 0 else 1
+            out.append((p + "conv1", p + "bn1", cin if b == 0 else cout, cout, 3, s, 1))
+            out.append((p + "conv2", p + "bn2", cout, cout, 3, 1, 1))
+            if li > 1 and b == 0:
+                out.append((p + "downsample.0", p + "downsample.1", cin, cout, 1, 2, 0))
+        cin = cout
+    return out
+
+
+def make_flows(n, seed=0):
+    """n smooth ego-motion-like optical-flow fields [n, 224, 224, 2] float32 (pixels): a global translation, an in-plane rotation
+    and a divergence (forward motion) about a random centre, plus three low-frequency sinusoids per channel; |flow| up to ~20 px."""
+    g = np.random.default_rng([int(seed), 0xF10])
+    ax = np.arange(FLOW_IMG, dtype=np.float64)
+    yy, xx = np.meshgrid(ax, ax, indexing="ij")
+    out = np.empty((n, FLOW_IMG, FLOW_IMG, 2), np.float32)
+    for i in range(n):
+        cx, cy = g.uniform(60, 164, 2)
+        t = g.uniform(-6, 6, 2)
+        w, d = g.uniform(-0.04, 0.04), g.uniform(-0.05, 0.05)
+        u = t[0] - w * (yy - cy) + d * (xx - cx)
+        v = t[1] + w * (xx - cx) + d * (yy - cy)
+        for f in (u, v):
+            for _ in range(3):
+                a, fx, fy, ph = g.uniform(-1.5, 1.5), g.uniform(0.5, 2.0), g.uniform(0.5, 2.0), g.uniform(0, 2 * np.pi)
+                f += a * np.sin(2 * np.pi * (fx * xx + fy * yy) / FLOW_IMG + ph)
+        out[i, ..., 0], out[i, ..., 1] = u, v
+    return out
+
+
+def _flow_cnn_calibrate(sd, flows):
+    """Set every BatchNorm's running statistics to the statistics of its input over `flows` (fp64 torch ops, eval-mode forward
+    with the statistics already set upstream), so that the activations stay O(1) through the network as in a trained one."""
+    F = torch.nn.functional
+    x = torch.from_numpy(flows).double()
+    x = torch.cat((x, torch.zeros(x.shape[:-1] + (1,), dtype=x.dtype)), -1).permute(0, 3, 1, 2)
+
+    def conv_bn(x, conv, bn, stride, pad, relu):
+        y = F.conv2d(x, sd[conv + ".weight"].double(), stride=stride, padding=pad)
+        mean = y.mean(dim=(0, 2, 3))
+        var = y.var(dim=(0, 2, 3), unbiased=True)
+        sd[bn + ".running_mean"] = mean.float()
+        sd[bn + ".running_var"] = var.float()
+        y = F.batch_norm(y, mean.float().double(), var.float().double(), sd[bn + ".weight"].double(), sd[bn + ".bias"].double(),
+                         False, 0.0, 1e-5)
+        return F.relu(y) if relu else y
+
+    convs = {c[0]: c for c in flow_cnn_convs()}
+    x = F.max_pool2d(conv_bn(x, "conv1", "bn1", 2, 3, True), 3, 2, 1)
+    for li in range(1, 5):
+        for b in range(2):
+            p = f"layer{li}.{b}."
+            _, _, _, _, _, s, _ = convs[p + "conv1"]
+            h = conv_bn(x, p + "conv1", p + "bn1", s, 1, True)
+            h = conv_bn(h, p + "conv2", p + "bn2", 1, 1, False)
+            idn = conv_bn(x, p + "downsample.0", p + "downsample.1", 2, 0, False) if (p + "downsample.0") in convs else x
+            x = F.relu(h + idn)
+
+
+def make_flow_cnn_weights(seed=0, prefix="cnn.resnet.", calib_frames=2):
+    """Seeded synthetic state dict of the reference's FeatureExtractor (resnet.py; 122 keys under `prefix`).  The reference
+    starts from ImageNet weights, which cannot be downloaded here.  Convolutions use torchvision's init (Kaiming normal, fan_out,
+    ReLU gain); BatchNorm affines are perturbed like make_stage1_weights' LayerNorms (1 + N(0, 0.1), N(0, 0.1)); the running
+    statistics are calibrated on make_flows(calib_frames) (fp64 torch ops); fc has PyTorch's default Linear init."""
+    sd = {}
+    for conv, bn, cin, cout, k, _, _ in flow_cnn_convs():
+        sd[conv + ".weight"] = _normal(seed, "flow." + conv, (cout, cin, k, k), np.sqrt(2.0 / (cout * k * k)))
+        sd[bn + ".weight"] = 1.0 + _normal(seed, "flow." + bn + ".weight", (cout,), 0.1)
+        sd[bn + ".bias"] = _normal(seed, "flow." + bn + ".bias", (cout,), 0.1)
+        sd[bn + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.long)
+    b = 1.0 / np.sqrt(FLOW_FEATS)
+    sd["fc.weight"] = _uniform(seed, "flow.fc.weight", (FLOW_FEATS, FLOW_FEATS), b)
+    sd["fc.bias"] = _uniform(seed, "flow.fc.bias", (FLOW_FEATS,), b)
+    _flow_cnn_calibrate(sd, make_flows(calib_frames, 1000 + seed))
+    return {prefix + k: v for k, v in sd.items()}

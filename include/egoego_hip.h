@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 7 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*) */
+#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*) */
 
 enum {
     EGOEGO_OK = 0,
@@ -335,6 +335,46 @@ int egoego_s1_integrate(const float* d_heads, int window, const int32_t* d_T, co
  * with w >= 0.  d_rot / d_trans / d_len as for egoego_s1_gravity_features; Rn, Ralign [S][3][3], scale [S], origin [S][3]. */
 int egoego_s1_gravity_apply(const float* d_rot, const float* d_trans, const int32_t* d_len, int S, int Lmax, const double* d_Rn,
                             const double* d_scale, const double* d_Ralign, const double* d_origin, double* d_pose, void* stream);
+
+/* ==================================================================================================================
+ * Stage 1's optical-flow feature extractor: FeatureExtractor (egoego/model/resnet.py = RN, lines 25-50), i.e. torchvision's
+ * resnet18 with fc = Linear(512, 512), in eval mode (BatchNorm with its running statistics, eps 1e-5), on 224 x 224 flow
+ * fields.  Every convolution and the fc run as split-bf16 implicit GEMMs (three bf16 MFMAs, fp32 accumulate) over fp32 NHWC
+ * activations.  Frames run in chunks of at most `chunk_frames` through a caller-allocated workspace; a frame's features are
+ * bit-identical whatever the chunk, the position or the other frames of the call.  egoego_flow_last_error() describes the last
+ * failure of an egoego_flow_* call.
+ * ================================================================================================================== */
+typedef struct egoego_flow_ctx egoego_flow_ctx;
+
+/* fp32 device tensors in the reference layout (the state dict of RN ResNet.resnet).  The 20 convolutions and their BatchNorms
+ * in this order: conv1 / bn1; then for layer1..layer4, block 0..1: conv1 / bn1, conv2 / bn2, and for block 0 of layer2..4
+ * downsample.0 / downsample.1 — i.e. index 0 stem, 1-4 layer1, 5-9 layer2, 10-14 layer3, 15-19 layer4.  conv_w[0] is
+ * (64, 3, 7, 7); its third input channel multiplies the reference's all-zero third flow channel and is not read. */
+typedef struct {
+    const float* conv_w[20];   /* (Cout, Cin, kh, kw) */
+    const float* bn_w[20];     /* (Cout) */
+    const float* bn_b[20];
+    const float* bn_mean[20];  /* running_mean */
+    const float* bn_var[20];   /* running_var */
+    const float* fc_w;         /* (512, 512) */
+    const float* fc_b;         /* (512) */
+} egoego_flow_weights;
+
+const char* egoego_flow_last_error(void);
+/* chunk_frames: frames per pass through the workspace (0 = the default, 256). */
+int egoego_flow_ctx_create(int device, int chunk_frames, egoego_flow_ctx** out);
+void egoego_flow_ctx_destroy(egoego_flow_ctx* ctx);
+/* RN:5-23 (ResNet.__init__): packs the convolution weights as [Cout][kh][kw][Cin] split-bf16 fragment-tiled planes and folds
+ * every BatchNorm into a per-channel fp32 scale = w / sqrt(var + 1e-5) and shift = b - mean * scale; synchronises `stream`. */
+int egoego_flow_load_weights(egoego_flow_ctx* ctx, const egoego_flow_weights* w, void* stream);
+/* Scratch bytes of a call over n_frames frames: min(n_frames, chunk_frames) frames' activations (0 if not accepted). */
+size_t egoego_flow_workspace_bytes(const egoego_flow_ctx* ctx, int n_frames);
+/* RN:38-50 (FeatureExtractor.forward) for N frames: d_flow [N][224][224][2] fp32 (the flow's two channels; the reference's
+ * appended zero channel is implied) -> d_out [N][512] fp32.  23 launches per chunk.  d_stages (optional, NULL = none): the
+ * activations after the stem (conv1, bn1, ReLU, max-pool) and after each of layer1..4, NHWC fp32, one array after the other:
+ * [N][56][56][64], [N][56][56][64], [N][28][28][128], [N][14][14][256], [N][7][7][512]. */
+int egoego_flow_features(egoego_flow_ctx* ctx, const float* d_flow, int n_frames, float* d_out, float* d_stages,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
