@@ -6,6 +6,7 @@ mirror of the reference's CondGaussianDiffusion interface in model.py.
 from .synthetic import ModelConfig, make_weights, make_head_windows, head_condition_mask  # noqa: F401
 from .synthetic import Stage1Config, make_stage1_weights  # noqa: F401
 from .synthetic import make_flow_cnn_weights, make_flows  # noqa: F401
+from .synthetic import make_body_model, make_body_poses  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch.cuda or the .so
@@ -15,6 +16,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name in ("HeadFormer", "HeadNormalFormer", "estimate_head_pose", "FlowFeatureExtractor", "split_headnet_state_dict"):
         from . import stage1
         return getattr(stage1, name)
+    if name in ("BodyModel", "BodyEngine", "run_smpl_model", "save_verts_faces_to_mesh_file"):
+        from . import body
+        return getattr(body, name)
     if name == "HipEngine":
         from .engine import HipEngine
         return HipEngine

@@ -63,6 +63,17 @@ class FlowWeights(C.Structure):
     _fields_ = [(n, C.c_void_p * FLOW_N_CONV) for n in ("conv_w", "bn_w", "bn_b", "bn_mean", "bn_var")] + [
         ("fc_w", C.c_void_p), ("fc_b", C.c_void_p)]
 
+
+BODY_N_JOINTS = 52
+BODY_POSE_FEATS = 9 * (BODY_N_JOINTS - 1)
+
+
+class BodyModelDesc(C.Structure):
+    """egoego_body_model"""
+    _fields_ = [(n, C.c_int32) for n in ("n_verts", "n_betas", "n_weights")] + [
+        (n, C.c_void_p) for n in ("v_template", "shapedirs", "posedirs", "j_template", "j_shapedirs", "skin_weight", "skin_joint",
+                                  "parents")]
+
 EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoego_ctx_destroy",
            "egoego_load_weights", "egoego_load_schedule", "egoego_workspace_bytes", "egoego_denoise",
            "egoego_p_sample", "egoego_sample_loop", "egoego_ddim_loop", "egoego_rot6d_to_matrix", "egoego_convert_model_res", "egoego_window_prefix", "egoego_window_condition",
@@ -70,7 +81,9 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_s1_last_error", "egoego_s1_ctx_create", "egoego_s1_ctx_destroy", "egoego_s1_load_weights",
            "egoego_s1_workspace_bytes", "egoego_s1_encode", "egoego_s1_gravity_features", "egoego_s1_integrate",
            "egoego_s1_gravity_apply", "egoego_flow_last_error", "egoego_flow_ctx_create", "egoego_flow_ctx_destroy",
-           "egoego_flow_load_weights", "egoego_flow_workspace_bytes", "egoego_flow_features"]
+           "egoego_flow_load_weights", "egoego_flow_workspace_bytes", "egoego_flow_features",
+           "egoego_body_last_error", "egoego_body_ctx_create", "egoego_body_ctx_destroy", "egoego_body_load_model",
+           "egoego_body_workspace_bytes", "egoego_body_forward"]
 OUTLIER_SITES = 16
 
 _lib = None
@@ -143,6 +156,14 @@ def load():
     lib.egoego_flow_workspace_bytes.argtypes = [vp, i32]
     lib.egoego_flow_workspace_bytes.restype = sz
     lib.egoego_flow_features.argtypes = [vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.egoego_body_last_error.restype = C.c_char_p
+    lib.egoego_body_ctx_create.argtypes = [i32, i32, C.POINTER(vp)]
+    lib.egoego_body_ctx_destroy.argtypes = [vp]
+    lib.egoego_body_ctx_destroy.restype = None
+    lib.egoego_body_load_model.argtypes = [vp, C.POINTER(BodyModelDesc), vp]
+    lib.egoego_body_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.egoego_body_workspace_bytes.restype = sz
+    lib.egoego_body_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -157,6 +178,11 @@ def check_s1(rc):
 def check_flow(rc):
     if rc != 0:
         raise EgoEgoHipError(f"libegoego_hip flow-CNN error {rc}: {load().egoego_flow_last_error().decode()}")
+
+
+def check_body(rc):
+    if rc != 0:
+        raise EgoEgoHipError(f"libegoego_hip body-model error {rc}: {load().egoego_body_last_error().decode()}")
 
 
 def check(rc):

@@ -326,3 +326,87 @@ def make_flow_cnn_weights(seed=0, prefix="cnn.resnet.", calib_frames=2):
     sd["fc.bias"] = _uniform(seed, "flow.fc.bias", (FLOW_FEATS,), b)
     _flow_cnn_calibrate(sd, make_flows(calib_frames, 1000 + seed))
     return {prefix + k: v for k, v in sd.items()}
+
+
+# ------------------------------------------------------------------------------------------ the SMPL-H body model
+BODY_N_JOINTS = 52
+_SMPLH_PARENTS_22 = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19)
+# rest offsets of the 22 body joints from their parents (metres, z up, arms along +-x): a rough adult in T-pose
+_BODY_OFFSETS_22 = (
+    (0, 0, 0.92), (0.07, 0, -0.09), (-0.07, 0, -0.09), (0, -0.02, 0.12), (0.03, 0, -0.39), (-0.03, 0, -0.39), (0, 0.02, 0.14),
+    (-0.01, -0.03, -0.41), (0.01, -0.03, -0.41), (0, 0.01, 0.06), (0.02, 0.12, -0.06), (-0.02, 0.12, -0.06), (0, -0.02, 0.21),
+    (0.08, -0.02, 0.12), (-0.08, -0.02, 0.12), (0, 0.04, 0.09), (0.10, -0.01, 0.04), (-0.10, -0.01, 0.04), (0.26, -0.01, -0.01),
+    (-0.26, -0.01, -0.01), (0.25, 0, 0), (-0.25, 0, 0))
+
+
+def body_model_parents():
+    """The 52 parents of the SMPL-H tree: the 22 body joints, then 15 joints per hand (five fingers of three joints, each finger
+    a chain from the wrist: joints 22-36 from the left wrist 20, joints 37-51 from the right wrist 21)."""
+    par = list(_SMPLH_PARENTS_22)
+    for wrist in (20, 21):
+        for _ in range(5):
+            par += [wrist, len(par), len(par) + 1]
+    return np.asarray(par, np.int64)
+
+
+def make_body_model(seed=0, n_verts=6890, n_faces=13776, max_weights=4):
+    """A seeded model in the layout of SMPL-H's model.npz (the licensed files cannot be shipped), as a dict of numpy arrays:
+    v_template (V, 3), shapedirs (V, 3, 16), posedirs (V, 3, 459), J_regressor (52, V), weights (V, 52), kintree_table (2, 52)
+    uint32 and f (n_faces, 3) uint32.  The vertices sit around the bones of a 1.7 m T-pose skeleton; posedirs and shapedirs
+    are uniform in +-1e-2; each J_regressor row averages a few vertices near its joint (rows sum to 1); every vertex has between
+    1 and `max_weights` non-zero skinning weights (its own joint, then joints up and down the tree) that sum to 1, and vertex 0
+    has exactly `max_weights`."""
+    V, NJ = int(n_verts), BODY_N_JOINTS
+    if V < NJ or not 1 <= max_weights <= NJ:
+        raise ValueError("make_body_model: n_verts >= 52 and 1 <= max_weights <= 52 expected")
+    g = np.random.default_rng([int(seed), 0xB0D1])
+    par = body_model_parents()
+    J = np.zeros((NJ, 3))
+    for j in range(NJ):
+        if j < 22:
+            off = np.asarray(_BODY_OFFSETS_22[j], np.float64)
+        else:  # fingers fan out from the wrist along the arm's direction
+            side = 1.0 if j < 37 else -1.0
+            k = (j - 22) % 15
+            off = np.array([side * (0.035 if k % 3 else 0.08), 0.012 * (k // 3 - 2) if k % 3 == 0 else 0.0, 0.0])
+        J[j] = off + (J[par[j]] if j else 0.0)
+    owner = np.concatenate([np.arange(NJ), g.integers(0, NJ, V - NJ)])  # every joint owns at least one vertex
+    radius = np.where(owner < 22, 0.06, 0.008)[:, None]
+    along = g.uniform(0, 1, (V, 1)) * (J[owner] - J[np.maximum(par[owner], 0)]) * (owner > 0)[:, None]
+    v_template = J[owner] - 0.5 * along + g.standard_normal((V, 3)) * radius
+    shapedirs = g.uniform(-1e-2, 1e-2, (V, 3, 16))
+    posedirs = g.uniform(-1e-2, 1e-2, (V, 3, 9 * (NJ - 1))).astype(np.float32)
+    # J_regressor: up to eight of the vertices each joint owns
+    J_regressor = np.zeros((NJ, V))
+    for j in range(NJ):
+        mine = np.flatnonzero(owner == j)[:8]
+        w = g.uniform(0.5, 1.5, mine.size)
+        J_regressor[j, mine] = w / w.sum()
+    # skinning weights: the owner first, then its ancestors, then the remaining joints, in a seeded order
+    weights = np.zeros((V, NJ))
+    count = g.integers(1, max_weights + 1, V)
+    count[0] = max_weights
+    for v in range(V):
+        chain, j = [], owner[v]
+        while j >= 0:
+            chain.append(j)
+            j = par[j]
+        if count[v] > len(chain):
+            rest = np.setdiff1d(np.arange(NJ), chain)
+            chain += list(g.permutation(rest))
+        js = np.asarray(chain[:count[v]])
+        w = g.uniform(0.2, 1.0, js.size) * np.r_[2.0, np.ones(js.size - 1)]
+        weights[v, js] = w / w.sum()
+    w32 = weights.astype(np.float32)
+    f = g.integers(0, V, (int(n_faces), 3)).astype(np.uint32)
+    kintree = np.stack([par, np.arange(NJ)]).astype(np.uint32)  # parents[0] = 2^32 - 1, as in the real file
+    return {"v_template": v_template.astype(np.float32), "shapedirs": shapedirs.astype(np.float32), "posedirs": posedirs,
+            "J_regressor": J_regressor.astype(np.float32), "weights": w32, "kintree_table": kintree, "f": f}
+
+
+def make_body_poses(n_frames, n_joints=52, seed=0, amplitude=math.pi / 2, trans_scale=3.0):
+    """Seeded poses for the body model: axis-angle [n_frames, n_joints, 3] with every component uniform in +-amplitude / sqrt(3)
+    (angles up to `amplitude`) and translations [n_frames, 3] of a few metres, float32."""
+    g = np.random.default_rng([int(seed), 0xB0D2])
+    aa = g.uniform(-1, 1, (n_frames, n_joints, 3)) * (amplitude / math.sqrt(3.0))
+    return aa.astype(np.float32), (g.standard_normal((n_frames, 3)) * trans_scale).astype(np.float32)

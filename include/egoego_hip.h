@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*) */
+#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*) was added under 8: purely additive, no existing entry changed */
 
 enum {
     EGOEGO_OK = 0,
@@ -375,6 +375,51 @@ size_t egoego_flow_workspace_bytes(const egoego_flow_ctx* ctx, int n_frames);
  * [N][56][56][64], [N][56][56][64], [N][28][28][128], [N][14][14][256], [N][7][7][512]. */
 int egoego_flow_features(egoego_flow_ctx* ctx, const float* d_flow, int n_frames, float* d_out, float* d_stages,
                          void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ==================================================================================================================
+ * The SMPL-H body model: what run_smpl_model (egoego/data/amass_diffusion_dataset.py = AD, lines 15-81) reaches through
+ * human_body_prior's BodyModel — shape blend, Rodrigues, pose-corrective blend shapes, the kinematic chain and linear-blend
+ * skinning, 52 joints, any vertex count.  The pose blend shapes run as one split-bf16 GEMM (three bf16 MFMAs, fp32 accumulate)
+ * with the skinning fused into its epilogue; the per-frame geometry is fp64, one thread per frame.  Frames run in chunks of at
+ * most `chunk_frames` through a caller-allocated workspace; a frame's vertices are bit-identical whatever the chunk, the
+ * position or the other frames of the call.  egoego_body_last_error() describes the last failure of an egoego_body_* call.
+ * ================================================================================================================== */
+typedef struct egoego_body_ctx egoego_body_ctx;
+
+/* Device tensors.  j_template = J_regressor . v_template and j_shapedirs = J_regressor . shapedirs are computed by the caller
+ * (fp64, rounded once); the skinning weights come compressed to n_weights (joint, weight) pairs per vertex, pair k of vertex v
+ * at [k][v], padded with (0, 0.0f). */
+typedef struct {
+    int32_t n_verts;
+    int32_t n_betas;
+    int32_t n_weights;           /* 1..52 */
+    const float* v_template;     /* (V, 3) */
+    const float* shapedirs;      /* (V, 3, n_betas) */
+    const float* posedirs;       /* (V, 3, 459), k = 9 (joint - 1) + 3 row + col of R - I */
+    const float* j_template;     /* (52, 3) */
+    const float* j_shapedirs;    /* (52, 3, n_betas) */
+    const float* skin_weight;    /* (n_weights, V) */
+    const int32_t* skin_joint;   /* (n_weights, V) */
+    const int32_t* parents;      /* (52): kintree_table[0]; parents[j] < j for j >= 1, parents[0] is not read */
+} egoego_body_model;
+
+const char* egoego_body_last_error(void);
+/* chunk_frames: frames per pass through the workspace (0 = the default, 8192). */
+int egoego_body_ctx_create(int device, int chunk_frames, egoego_body_ctx** out);
+void egoego_body_ctx_destroy(egoego_body_ctx* ctx);
+/* Copies the model and packs posedirs into split-bf16 fragment-tiled planes (rows ordered so that the x, y and z of a vertex
+ * fall to one lane, K padded to 480); synchronises `stream`. */
+int egoego_body_load_model(egoego_body_ctx* ctx, const egoego_body_model* m, void* stream);
+/* Scratch bytes of a call over n_frames frames of n_seqs sequences (0 if not accepted or no model is loaded). */
+size_t egoego_body_workspace_bytes(const egoego_body_ctx* ctx, int n_frames, int n_seqs);
+/* N frames: d_root_orient [N][3], d_pose_body [N][63], d_pose_hand [N][90] (NULL = identity hand rotations: K runs over the 21
+ * body joints only, bit-identical to a zero hand pose), d_trans [N][3], axis-angle fp32; d_betas [n_seqs][n_betas] and
+ * d_seq int32 [N], each frame's row of d_betas -> d_verts [N][V][3], d_joints [N][52][3] fp32.  d_pose_offsets (optional,
+ * NULL = none): [N][V][3], the pose-corrective offsets posedirs . (R - I) alone.  Two launches per call and two per chunk. */
+int egoego_body_forward(egoego_body_ctx* ctx, const float* d_root_orient, const float* d_pose_body, const float* d_pose_hand,
+                        const float* d_trans, const float* d_betas, const int32_t* d_seq, int n_frames, int n_seqs,
+                        float* d_verts, float* d_joints, float* d_pose_offsets, void* d_workspace, size_t workspace_bytes,
+                        void* stream);
 
 #ifdef __cplusplus
 }

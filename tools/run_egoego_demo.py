@@ -13,7 +13,14 @@
 
 Writes an npz with the stage-1 head pose [B, T, 7], the local axis-angle [B, T', 22, 3], the root [B, T', 3] and the global joints
 [B, T', 22, 3], and prints one JSON line with the stage-1 and stage-2 wall times.  Not done: get_head_vel (computed but never used
-by the reference), determine_floor_height_and_contacts (the floor-height shift after FK) and the visualisation.
+by the reference), determine_floor_height_and_contacts (the floor-height shift after FK) and, without --body_model, the
+visualisation.
+
+  --body_model DIR      the reference's smpl_models/smplh_amass layout (male/model.npz, female/model.npz).  With --gen_vis, the
+                        first sample of every sequence goes through the SMPL-H body model as in gen_full_body_vis (male, zero
+                        betas; run_egoego.py:161-166 first moves the first frame's head to x = y = 0): the npz gains mesh_verts
+                        [T', V, 3], mesh_jnts [T', 22, 3] and mesh_shift [3] (the translation applied) of the first sequence,
+                        and <--vis_folder>/<sequence>/objs gets one OBJ file per frame.  Blender rendering stays not done.
 """
 import argparse
 import json
@@ -65,7 +72,9 @@ def parse_opt(argv=None):
     p.add_argument("--diffusion_d_model", type=int, default=512)
     p.add_argument("--use_min_max", action="store_true", help="accepted for flag compatibility")
     p.add_argument("--canonicalize_init_head", action="store_true", help="accepted for flag compatibility")
-    p.add_argument("--gen_vis", action="store_true", help="accepted for flag compatibility (no visualisation)")
+    p.add_argument("--gen_vis", action="store_true", help="with --body_model: write the body meshes (otherwise accepted and ignored)")
+    p.add_argument("--body_model", default="", help="folder with male/model.npz (SMPL-H); enables --gen_vis")
+    p.add_argument("--vis_folder", default="", help="where the OBJ folders go (default: egoego_demo_on_ares next to --out)")
     # assets
     p.add_argument("--data_root_folder", required=True)
     p.add_argument("--weight_root_folder", default="")
@@ -115,6 +124,16 @@ def build_stage2(opt, dev):
     return model, note
 
 
+def gen_full_body_vis(bm_dict, root_trans, local_aa, mesh_folder):
+    """trainer_amass_cond_motion_diffusion.py:348-382 without the rendering: root_trans [T, 3], local_aa [T, 22, 3] -> mesh joints
+    [T, 22, 3], vertices [T, V, 3]; the OBJ files go to `mesh_folder`."""
+    from egoego_release_amd import body
+    betas = torch.zeros(1, 16, device=root_trans.device)
+    jnts, verts, faces = body.run_smpl_model(root_trans[None].float(), local_aa[None].float(), betas, ["male"], bm_dict)
+    body.save_verts_faces_to_mesh_file(verts[0].cpu().numpy(), faces.cpu().numpy(), mesh_folder)
+    return jnts[0], verts[0]
+
+
 def main(argv=None):
     opt = parse_opt(argv)
     dev = torch.device("cuda", int(opt.device))
@@ -126,6 +145,12 @@ def main(argv=None):
     batches = stage1.load_ares_demo(opt.data_root_folder)
     torch.manual_seed(opt.seed)
     out = {"head_pose": [], "local_aa": [], "root_trans": [], "global_jpos": []}
+    vis = bool(opt.body_model and opt.gen_vis)
+    mesh, mesh_folders, t3 = {}, [], 0.0
+    if vis:
+        from egoego_release_amd import body
+        bm_dict = {"male": body.BodyModel(os.path.join(opt.body_model, "male", "model.npz"), num_betas=16, device=dev)}
+        vis_folder = opt.vis_folder or os.path.join(os.path.dirname(os.path.abspath(opt.out)), "egoego_demo_on_ares")
     t1 = t2 = 0.0
     names = []
     for batch in batches:
@@ -146,11 +171,28 @@ def main(argv=None):
         t1, t2 = t1 + (b - a), t2 + (c - b)
         for k, v in (("head_pose", hp), ("local_aa", aa), ("root_trans", root), ("global_jpos", gj)):
             out[k].append(v.detach().cpu().numpy())
-    np.savez_compressed(opt.out, **{k: np.concatenate(v) for k, v in out.items()})
+        if vis:
+            move = gj[:, 0:1, 15:16, :].clone()  # run_egoego.py:161-166: the first frame's head to x = y = 0
+            move[..., 2] = 0
+            # run_egoego.py:166 takes the root JOINT position of the moved FK result (pred_fk_jpos[:, :, 0, :], rest offset
+            # included) and :191 hands it to gen_full_body_vis as root_trans, so the body model adds its own J_0 on top: the
+            # mesh sits J_0 away from the FK skeleton.  Kept as the reference does it, so the OBJ files agree with its output.
+            vis_root = (gj - move)[0, :, 0, :]
+            folder = os.path.join(vis_folder, str(batch["seq_name"][0]).replace(" ", ""), "objs")
+            jn, vt = gen_full_body_vis(bm_dict, vis_root, aa[0], folder)
+            torch.cuda.synchronize()
+            t3 += time.perf_counter() - c
+            mesh_folders.append(folder)
+            if not mesh:
+                mesh = {"mesh_verts": vt.cpu().numpy(), "mesh_jnts": jn.cpu().numpy(), "mesh_shift": -move[0, 0, 0].cpu().numpy()}
+    np.savez_compressed(opt.out, **{k: np.concatenate(v) for k, v in out.items()}, **mesh)
     rep = {"sequences": names, "frames": int(out["head_pose"][0].shape[1]), "samples": opt.diffusion_batch_size,
            "stage1_seconds": round(t1, 4), "stage2_seconds": round(t2, 4), "diffusion_steps": opt.timesteps, "weights": notes,
            "not_done": ["floor-height shift (determine_floor_height_and_contacts)", "get_head_vel", "visualisation"],
            "out": opt.out}
+    if vis:
+        rep["not_done"][2] = "Blender rendering of the meshes"
+        rep.update(mesh_seconds=round(t3, 4), mesh_folders=mesh_folders)
     print(json.dumps(rep), flush=True)
     return rep
 
