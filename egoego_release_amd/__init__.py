@@ -7,6 +7,7 @@ from .synthetic import ModelConfig, make_weights, make_head_windows, head_condit
 from .synthetic import Stage1Config, make_stage1_weights  # noqa: F401
 from .synthetic import make_flow_cnn_weights, make_flows  # noqa: F401
 from .synthetic import make_body_model, make_body_poses  # noqa: F401
+from .synthetic import make_eval_motion  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch.cuda or the .so
@@ -19,6 +20,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name in ("BodyModel", "BodyEngine", "run_smpl_model", "save_verts_faces_to_mesh_file"):
         from . import body
         return getattr(body, name)
+    if name in ("evaluate_samples", "determine_floor_height_and_contacts", "compute_metrics_for_smpl"):
+        from . import evaluate
+        return getattr(evaluate, name)
     if name == "HipEngine":
         from .engine import HipEngine
         return HipEngine

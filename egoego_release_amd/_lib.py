@@ -83,7 +83,12 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_s1_gravity_apply", "egoego_flow_last_error", "egoego_flow_ctx_create", "egoego_flow_ctx_destroy",
            "egoego_flow_load_weights", "egoego_flow_workspace_bytes", "egoego_flow_features",
            "egoego_body_last_error", "egoego_body_ctx_create", "egoego_body_ctx_destroy", "egoego_body_load_model",
-           "egoego_body_workspace_bytes", "egoego_body_forward"]
+           "egoego_body_workspace_bytes", "egoego_body_forward",
+           "egoego_eval_last_error", "egoego_eval_max_frames", "egoego_eval_fk", "egoego_eval_shift_xy",
+           "egoego_eval_floor_contacts", "egoego_eval_metrics", "egoego_eval_root_to_floor", "egoego_eval_best"]
+EVAL_METRIC_KEYS = ("root_dist", "root_rot_dist", "root_trans_dist", "head_dist", "head_rot_dist", "head_trans_dist", "mpjpe",
+                    "mpjpe_wo_hand", "accel_pred", "accel_gt", "accel_err", "pred_fs", "gt_fs")  # then single_jpe[22]
+EVAL_N_METRICS = len(EVAL_METRIC_KEYS) + 22
 OUTLIER_SITES = 16
 
 _lib = None
@@ -164,6 +169,14 @@ def load():
     lib.egoego_body_workspace_bytes.argtypes = [vp, i32, i32]
     lib.egoego_body_workspace_bytes.restype = sz
     lib.egoego_body_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.egoego_eval_last_error.restype = C.c_char_p
+    lib.egoego_eval_max_frames.restype = i32
+    lib.egoego_eval_fk.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), i32, vp, vp, vp]
+    lib.egoego_eval_shift_xy.argtypes = [vp, i32, i32, i32, vp]
+    lib.egoego_eval_floor_contacts.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.egoego_eval_metrics.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.egoego_eval_root_to_floor.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.egoego_eval_best.argtypes = [vp, i32, vp, i32, i32, vp, vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -183,6 +196,11 @@ def check_flow(rc):
 def check_body(rc):
     if rc != 0:
         raise EgoEgoHipError(f"libegoego_hip body-model error {rc}: {load().egoego_body_last_error().decode()}")
+
+
+def check_eval(rc):
+    if rc != 0:
+        raise EgoEgoHipError(f"libegoego_hip evaluation error {rc}: {load().egoego_eval_last_error().decode()}")
 
 
 def check(rc):

@@ -410,3 +410,169 @@ def make_body_poses(n_frames, n_joints=52, seed=0, amplitude=math.pi / 2, trans_
     g = np.random.default_rng([int(seed), 0xB0D2])
     aa = g.uniform(-1, 1, (n_frames, n_joints, 3)) * (amplitude / math.sqrt(3.0))
     return aa.astype(np.float32), (g.standard_normal((n_frames, 3)) * trans_scale).astype(np.float32)
+
+
+# ---------------------------------------------------------------- evaluation inputs
+EVAL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19)
+# a stand-in 22-joint skeleton, z up, metres: the toes of the rest pose sit 0.93 below the hips
+EVAL_REST_OFFSETS = (
+    (0, 0, 0), (0.07, 0, -0.09), (-0.07, 0, -0.09), (0, 0, 0.11), (0, 0, -0.38), (0, 0, -0.38), (0, 0, 0.13), (0, 0, -0.40),
+    (0, 0, -0.40), (0, 0, 0.05), (0, 0.12, -0.06), (0, 0.12, -0.06), (0, 0, 0.21), (0.08, 0, 0.12), (-0.08, 0, 0.12), (0, 0, 0.09),
+    (0.10, 0, 0.03), (-0.10, 0, 0.03), (0.26, 0, 0), (-0.26, 0, 0), (0.25, 0, 0), (-0.25, 0, 0))
+EVAL_CONTACT_JOINTS = (10, 11, 7, 8, 20, 21, 4, 5)  # toes, feet, hands, legs: the joints with a contact channel
+
+
+def eval_fk(root_trans, local_aa, rest_offsets=EVAL_REST_OFFSETS, parents=EVAL_PARENTS):
+    """fp64 forward kinematics by rotation matrices: root_trans [N, 3], local_aa [N, 22, 3] -> joints [N, 22, 3]."""
+    aa = np.asarray(local_aa, np.float64)
+    ang = np.linalg.norm(aa, axis=-1)[..., None, None]
+    ax = aa / np.where(ang[..., 0] == 0, 1.0, ang[..., 0])
+    K = np.zeros(aa.shape[:-1] + (3, 3))
+    K[..., 0, 1], K[..., 0, 2], K[..., 1, 0] = -ax[..., 2], ax[..., 1], ax[..., 2]
+    K[..., 1, 2], K[..., 2, 0], K[..., 2, 1] = -ax[..., 0], -ax[..., 1], ax[..., 0]
+    R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * (K @ K)
+    rest = np.asarray(rest_offsets, np.float64)
+    G, P = [R[:, 0]], [np.broadcast_to(rest[0], (aa.shape[0], 3))]
+    for j in range(1, 22):
+        p = parents[j]
+        P.append(np.einsum("nab,b->na", G[p], rest[j]) + P[p])
+        G.append(G[p] @ R[:, j])
+    return np.stack(P, 1) + np.asarray(root_trans, np.float64)[:, None]
+
+
+def _eval_dbscan(h, eps=0.005, min_samples=3):
+    """DBSCAN for 1-D points by its textbook definition (neighbour lists, clusters grown from the cores in input order), fp64."""
+    n = h.size
+    near = np.abs(h[:, None] - h[None, :]) <= eps
+    core = near.sum(1) >= min_samples
+    labels = np.full(n, -1)
+    k = 0
+    for i in range(n):
+        if labels[i] != -1 or not core[i]:
+            continue
+        labels[i] = k
+        stack = [i]
+        while stack:
+            c = stack.pop()
+            if core[c]:
+                for j in np.flatnonzero(near[c] & (labels == -1)):
+                    labels[j] = k
+                    stack.append(j)
+        k += 1
+    return labels
+
+
+def assert_eval_margins(joints, fps=30, rel=1e-4):
+    """Asserts, in fp64, that nothing determine_floor_height_and_contacts thresholds on `joints` [T, 22, 3] (float32 values) lies
+    within a relative `rel` of its threshold, so that an exact comparison of its discrete outputs is no coin toss: the eight
+    velocities against 0.005; every pairwise gap of static toe heights against eps = 0.005; the two smallest group medians against
+    each other; the contact heights against 0.04 / 0.08; the terrain, root and size tests of the discard flag.  Returns the fp64
+    floor height (None without a static sample)."""
+    x = np.asarray(joints, np.float32).astype(np.float64)
+    T = x.shape[0]
+    assert T >= 2
+
+    def clear(v, thr, what):
+        v = np.asarray(v, np.float64)
+        bad = np.abs(v - thr) < rel * abs(thr)
+        assert not bad.any(), f"{what}: {v[bad][:3]} within {rel} of the threshold {thr}"
+
+    vel = []
+    for j in EVAL_CONTACT_JOINTS:
+        v = np.linalg.norm(x[1:, j] - x[:-1, j], axis=1)
+        vel.append(np.append(v, v[-1]))
+    vel = np.stack(vel)
+    clear(vel, 0.005, "a joint velocity")
+    frames = np.arange(T)
+    h = np.append(x[vel[0] < 0.005, 10, 2], x[vel[1] < 0.005, 11, 2])
+    idx = np.append(frames[vel[0] < 0.005], frames[vel[1] < 0.005])
+    if h.size == 0:
+        floor = 0.0
+    else:
+        s = np.sort(h)
+        for k in range(1, min(s.size, 64)):  # gaps of sorted samples k apart; they only grow with k
+            g = s[k:] - s[:-k]
+            clear(g, 0.005, "a gap of static heights")
+            if g.min() > 0.005 * (1 + rel):
+                break
+        else:
+            clear(np.abs(h[:, None] - h[None, :]), 0.005, "a gap of static heights")
+        labels = _eval_dbscan(h)
+        groups = np.unique(labels)
+        med = np.array([np.median(h[labels == g]) for g in groups])
+        root_med = np.array([np.median(x[np.unique(idx[labels == g]), 0, 2]) for g in groups])
+        size = np.array([(labels == g).sum() for g in groups])
+        order = np.argsort(med, kind="stable")
+        floor = med[order[0]]
+        if med.size > 1:
+            assert med[order[1]] - floor > rel * max(abs(floor), 0.005), "the two smallest group medians are closer than the margin"
+        clear(med - floor, 0.04, "a group median above the floor")
+        clear(root_med - root_med[order[0]], 0.04, "a group's root median above the floor group's")
+        assert not np.any(size == int(0.25 * fps) + 0.5)
+    for k, j in enumerate(EVAL_CONTACT_JOINTS):
+        clear(x[:, j, 2] - floor, 0.04 if k < 2 else 0.08, "a contact height")
+    return floor if h.size else None
+
+
+def make_eval_motion(B, T, seed=0, noise=0.05, fps=30, lengths=None, check=True):
+    """Walking-like motions for the evaluation tests: a ground-truth sequence and B samples around it, as local axis-angle
+    [.., T, 22, 3] and root translation [.., T, 3] over EVAL_REST_OFFSETS.  The body alternates stance phases (pose and root held
+    for 4-9 frames, so the toes rest at the height the held pose gives them) and steps (linear moves of 5-9 frames, at least 4 cm
+    per frame).  Sample b adds `noise` * (b + 1) / B of a seeded perturbation to the key poses and roots.
+
+    Asserts (assert_eval_margins, on the fp64 joints rounded to float32, after the xy shift by the first frame's head, over each
+    sample's `lengths[b]` frames) that no thresholded quantity lies within a relative 1e-4 of its threshold, and that the two
+    smallest mpjpe values differ by more than that (`check=False` skips both, for timing runs: long sequences hold too many
+    static samples for every pairwise gap to clear eps by chance).  Returns a dict of float32 numpy arrays: local_aa, root_trans, gt_local_aa,
+    gt_root_trans, rest_offsets, and parents."""
+    g = np.random.default_rng([int(seed), 0xE7A1])
+    seg = []
+    t = 0
+    while t < T:
+        hold, move = int(g.integers(4, 10)), int(g.integers(5, 10))
+        seg.append((t, hold, move))
+        t += hold + move
+    nk = len(seg) + 1
+    amp = np.full((22, 1), 0.12)
+    amp[[1, 2, 4, 5, 7, 8]] = 0.3
+    key_aa = g.uniform(-1, 1, (nk, 22, 3)) * amp
+    key_root = np.zeros((nk, 3))
+    key_root[:, 1] = np.arange(nk) * 0.45 + g.uniform(-0.05, 0.05, nk)
+    key_root[:, 0] = g.uniform(-0.1, 0.1, nk)
+    key_root[:, 2] = 0.93 + g.uniform(-0.02, 0.02, nk)
+    d_aa, d_root = g.standard_normal((B, nk, 22, 3)), g.standard_normal((B, nk, 3))
+
+    def expand(ka, kr):
+        aa, root = np.zeros((T, 22, 3)), np.zeros((T, 3))
+        for k, (t0, hold, move) in enumerate(seg):
+            for i in range(hold + move):
+                if t0 + i >= T:
+                    break
+                w = 0.0 if i < hold else (i - hold + 1) / (move + 1)
+                aa[t0 + i] = (1 - w) * ka[k] + w * ka[k + 1]
+                root[t0 + i] = (1 - w) * kr[k] + w * kr[k + 1]
+        return aa.astype(np.float32), root.astype(np.float32)
+
+    gt_aa, gt_root = expand(key_aa, key_root)
+    aa, root = np.zeros((B, T, 22, 3), np.float32), np.zeros((B, T, 3), np.float32)
+    lengths = [T] * B if lengths is None else [int(v) for v in lengths]
+    rest32 = np.asarray(EVAL_REST_OFFSETS, np.float32)  # what a caller passes on
+    gt_j = eval_fk(gt_root, gt_aa, rest32).astype(np.float32)
+    gt_j[:, :, :2] -= gt_j[0, 15, :2].copy()
+    mpjpe = []
+    for b in range(B):
+        s = noise * (b + 1) / B
+        aa[b], root[b] = expand(key_aa + s * d_aa[b] * amp, key_root + s * 0.3 * d_root[b])
+        if not check:
+            continue
+        L = lengths[b]
+        j = eval_fk(root[b, :L], aa[b, :L], rest32).astype(np.float32)
+        j[:, :, :2] -= j[0, 15, :2].copy()
+        assert_eval_margins(j, fps)
+        e = (j.astype(np.float64) - j[:, :1]) - (gt_j[:L].astype(np.float64) - gt_j[:L, :1])
+        mpjpe.append(np.linalg.norm(e, axis=2).mean() * 1000)
+    if B > 1 and check:
+        lo = np.sort(mpjpe)[:2]
+        assert lo[1] - lo[0] > 1e-4 * lo[1], "the two smallest mpjpe values are closer than the margin"
+    return {"local_aa": aa, "root_trans": root, "gt_local_aa": gt_aa, "gt_root_trans": gt_root,
+            "rest_offsets": rest32, "parents": EVAL_PARENTS}

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*) was added under 8: purely additive, no existing entry changed */
+#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*) and the evaluation (egoego_eval_*) were added under 8: purely additive, no existing entry changed */
 
 enum {
     EGOEGO_OK = 0,
@@ -420,6 +420,47 @@ int egoego_body_forward(egoego_body_ctx* ctx, const float* d_root_orient, const 
                         const float* d_trans, const float* d_betas, const int32_t* d_seq, int n_frames, int n_seqs,
                         float* d_verts, float* d_joints, float* d_pose_offsets, void* d_workspace, size_t workspace_bytes,
                         void* stream);
+
+/* ==================================================================================================================
+ * Batched evaluation of sampled motions: what the reference's evaluation loop (eval_egoego.py:358-446) does per sample on the
+ * host — fk_smpl, determine_floor_height_and_contacts (utils/data_utils/process_amass_dataset.py:160-338, with sklearn's
+ * DBSCAN restated on the sorted line) and compute_metrics_for_smpl (kinpoly/scripts/eval_metrics_imu_rec.py:264-342) — for B
+ * sequences of 22 joints at once.  Every tensor is a device tensor; sequences are padded to T frames and d_lengths (int32 [B],
+ * NULL = all T) gives each one's real length; padded frames are never read into a result.  The entries keep no state.  A
+ * sequence's results are bit-identical alone, at any position of a batch and under any padded T.
+ * egoego_eval_last_error() describes the last failure of an egoego_eval_* call.
+ * ================================================================================================================== */
+const char* egoego_eval_last_error(void);
+/* The longest sequence egoego_eval_floor_contacts accepts (4096): 2 T static-height samples are kept in LDS. */
+int egoego_eval_max_frames(void);
+/* fk_smpl for N frames: d_root [N][3], d_aa [N][22][3] local axis-angle, d_rest_offsets [22][3]; parents_host: 22 ints on the
+ * host, parents[j] < j for j >= 1 -> d_quat [N][22][4] global rotations (w, x, y, z; w >= 0), d_jpos [N][22][3].  fp64 inside,
+ * rounded once. */
+int egoego_eval_fk(const float* d_root, const float* d_aa, const float* d_rest_offsets, const int32_t* parents_host, int n_frames,
+                   float* d_quat, float* d_jpos, void* stream);
+/* d_jpos [B][T][22][3], in place: every joint of sequence b moves by minus the xy of `joint` in its first frame. */
+int egoego_eval_shift_xy(float* d_jpos, int B, int T, int joint, void* stream);
+/* determine_floor_height_and_contacts for B sequences d_jpos [B][T][22][3] (z up), T <= egoego_eval_max_frames():
+ * d_floor_height, d_offset_floor_height (= floor - 0.01; both 0 without a static toe sample) [B] fp32; d_contacts [B][T][22]
+ * fp32 0 / 1 (zero on padded frames); d_discard [B] int32; d_n_static [B]: the number of static toe samples n; d_n_groups [B]:
+ * clusters plus the noise group if any.  d_labels (optional, NULL = none): int32 [B][2 T], the DBSCAN label of each sample in
+ * the reference's order (left-toe frames, then right-toe frames), -1 = noise, -2 past n.  One workgroup per sequence. */
+int egoego_eval_floor_contacts(const float* d_jpos, const int32_t* d_lengths, int B, int T, float fps, float* d_floor_height,
+                               float* d_offset_floor_height, float* d_contacts, int32_t* d_discard, int32_t* d_labels,
+                               int32_t* d_n_static, int32_t* d_n_groups, void* stream);
+/* compute_metrics_for_smpl for B predictions d_pred_quat [B][T][22][4], d_pred_jpos [B][T][22][3] against the ground truth
+ * d_gt_quat / d_gt_jpos ([T]... shared by all when gt_shared != 0, else [B][T]...); floor heights [B] fp32 each.
+ * d_out [B][35] fp64: root_dist, root_rot_dist, root_trans_dist, head_dist, head_rot_dist, head_trans_dist, mpjpe,
+ * mpjpe_wo_hand, accel_pred, accel_gt, accel_err, pred_fs, gt_fs, then single_jpe[22]; the reference's units.  The
+ * acceleration terms need 3 frames (NaN below).  One workgroup per prediction; fp64 sums in a fixed order. */
+int egoego_eval_metrics(const float* d_gt_quat, const float* d_gt_jpos, int gt_shared, const float* d_gt_floor_height,
+                        const float* d_pred_quat, const float* d_pred_jpos, const float* d_pred_floor_height,
+                        const int32_t* d_lengths, int B, int T, double* d_out, void* stream);
+/* d_root [B][T][3] = joint 0 of d_jpos [B][T][22][3] with d_floor_height[b] taken off z. */
+int egoego_eval_root_to_floor(const float* d_jpos, const float* d_floor_height, int B, int T, float* d_root, void* stream);
+/* d_best [n_groups] int32: per group g the first b with d_group[b] == g (NULL = all 0) whose d_metrics[b][column] is smallest,
+ * -1 for an empty group. */
+int egoego_eval_best(const double* d_metrics, int column, const int32_t* d_group, int B, int n_groups, int32_t* d_best, void* stream);
 
 #ifdef __cplusplus
 }

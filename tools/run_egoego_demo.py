@@ -12,9 +12,11 @@
   --stats / --rest_offsets / --timesteps / --seed  as in tools/run_stage2_demo.py
 
 Writes an npz with the stage-1 head pose [B, T, 7], the local axis-angle [B, T', 22, 3], the root [B, T', 3] and the global joints
-[B, T', 22, 3], and prints one JSON line with the stage-1 and stage-2 wall times.  Not done: get_head_vel (computed but never used
-by the reference), determine_floor_height_and_contacts (the floor-height shift after FK) and, without --body_model, the
-visualisation.
+[B, T', 22, 3], and prints one JSON line with the stage-1 and stage-2 wall times.  The floor-height shift of run_egoego.py:161-173
+runs on the device (egoego_release_amd.evaluate): the npz also holds floor_height [B] (determine_floor_height_and_contacts at 30 fps
+on the joints moved so that the first frame's head is at x = y = 0) and root_trans_floor [B, T', 3], the moved root joint with that
+height taken off z.  Not done: get_head_vel (computed but never used by the reference) and, without --body_model, the visualisation.
+The meshes of --gen_vis keep their placement (mesh_shift); take floor_height off their z to stand them on the floor.
 
   --body_model DIR      the reference's smpl_models/smplh_amass layout (male/model.npz, female/model.npz).  With --gen_vis, the
                         first sample of every sequence goes through the SMPL-H body model as in gen_full_body_vis (male, zero
@@ -34,7 +36,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-from egoego_release_amd import harness, make_weights, ModelConfig, stage1  # noqa: E402
+from egoego_release_amd import evaluate, harness, make_weights, ModelConfig, stage1  # noqa: E402
 from egoego_release_amd.synthetic import make_stage1_weights  # noqa: E402
 import run_stage2_demo as S2  # noqa: E402
 
@@ -144,7 +146,7 @@ def main(argv=None):
     ds = harness.SkeletonStats(stats["global_jpos_min"], stats["global_jpos_max"], np.load(opt.rest_offsets), harness.SMPLH_PARENTS_22)
     batches = stage1.load_ares_demo(opt.data_root_folder)
     torch.manual_seed(opt.seed)
-    out = {"head_pose": [], "local_aa": [], "root_trans": [], "global_jpos": []}
+    out = {"head_pose": [], "local_aa": [], "root_trans": [], "global_jpos": [], "floor_height": [], "root_trans_floor": []}
     vis = bool(opt.body_model and opt.gen_vis)
     mesh, mesh_folders, t3 = {}, [], 0.0
     if vis:
@@ -166,10 +168,15 @@ def main(argv=None):
         n, t = aa.shape[:2]
         _, gj = ds.fk_smpl(root.reshape(-1, 3), aa.reshape(-1, 22, 3))
         gj = gj.reshape(n, t, 22, 3)
+        # run_egoego.py:161-173: the first frame's head to x = y = 0, then the root down by the floor height
+        moved = evaluate.shift_xy_(gj.float().clone())
+        floor, _, _ = evaluate.determine_floor_height_and_contacts(moved, 30)
+        root_floor = evaluate.root_to_floor(moved, floor)
         torch.cuda.synchronize()
         c = time.perf_counter()
         t1, t2 = t1 + (b - a), t2 + (c - b)
-        for k, v in (("head_pose", hp), ("local_aa", aa), ("root_trans", root), ("global_jpos", gj)):
+        for k, v in (("head_pose", hp), ("local_aa", aa), ("root_trans", root), ("global_jpos", gj), ("floor_height", floor),
+                     ("root_trans_floor", root_floor)):
             out[k].append(v.detach().cpu().numpy())
         if vis:
             move = gj[:, 0:1, 15:16, :].clone()  # run_egoego.py:161-166: the first frame's head to x = y = 0
@@ -188,10 +195,10 @@ def main(argv=None):
     np.savez_compressed(opt.out, **{k: np.concatenate(v) for k, v in out.items()}, **mesh)
     rep = {"sequences": names, "frames": int(out["head_pose"][0].shape[1]), "samples": opt.diffusion_batch_size,
            "stage1_seconds": round(t1, 4), "stage2_seconds": round(t2, 4), "diffusion_steps": opt.timesteps, "weights": notes,
-           "not_done": ["floor-height shift (determine_floor_height_and_contacts)", "get_head_vel", "visualisation"],
+           "not_done": ["get_head_vel", "visualisation"],
            "out": opt.out}
     if vis:
-        rep["not_done"][2] = "Blender rendering of the meshes"
+        rep["not_done"][1] = "Blender rendering of the meshes"
         rep.update(mesh_seconds=round(t3, 4), mesh_folders=mesh_folders)
     print(json.dumps(rep), flush=True)
     return rep

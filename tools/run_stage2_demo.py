@@ -18,7 +18,10 @@ of this repo: every asset is an input file, and without `--w
   --stats         the dataset's min/max statistics pickle (global_jpos_min / global_jpos_max, amass_diffusion_dataset.py:232-239)
   --rest_offsets  .npy [22,3] rest-pose joint offsets (AMASSDataset.rest_human_offsets; needs the licensed SMPL-H model to
                   produce); --parents optionally overrides the SMPL-H kintree
-  --gt_jpos       optional .npy [T,22,3] ground-truth global joints -> MPJPE (mm)
+  --gt_jpos       optional .npy [T,22,3] ground-truth global joints -> MPJPE (mm) and, under "metrics", the position keys of
+                  compute_metrics_for_smpl per sample (egoego_release_amd.evaluate, on the device; the foot sliding of the samples
+                  is measured from each sample's own floor height, the ground truth's from 0)
+  --gt_quat       optional .npy [T,22,4] ground-truth global rotations (w,x,y,z): adds the root / head rotation keys
 """
 import argparse
 import json
@@ -84,6 +87,7 @@ def parse_opt(argv=None):
     p.add_argument("--rest_offsets", required=True)
     p.add_argument("--parents", default="", help="comma-separated 22 parent indices (default: SMPL-H kintree)")
     p.add_argument("--gt_jpos", default="")
+    p.add_argument("--gt_quat", default="")
     p.add_argument("--timesteps", type=int, default=1000, help="diffusion steps (lower = truncated chain, for smoke runs)")
     p.add_argument("--sampling_rng", default="torch", choices=("torch", "philox"))
     p.add_argument("--seed", type=int, default=0)
@@ -189,7 +193,21 @@ def main(argv=None):
            "sharding": "by sequence (dist.harness_sharded)" if opt.gpus >= 1 else None}
     if opt.gt_jpos:
         gt = np.load(opt.gt_jpos)
+        from egoego_release_amd import evaluate
+        n = min(t, gt.shape[0])
+        edev = gj.device if gj.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        pj, pq = gj[:, :n].float().contiguous().to(edev), gq.reshape(b, t, 22, 4)[:, :n].float().contiguous().to(edev)
+        gt_j = torch.as_tensor(gt[:n], dtype=torch.float32, device=edev)
+        if opt.gt_quat:
+            gt_q = torch.as_tensor(np.load(opt.gt_quat)[:n], dtype=torch.float32, device=edev)
+        else:  # without rotations to compare against, the samples' own stand in and the rotation keys are left out
+            gt_q, gt_j = pq, gt_j[None].expand(b, -1, -1, -1)
+        floor = evaluate.determine_floor_height_and_contacts(pj, 30)[0] if 2 <= n <= evaluate.MAX_FRAMES else 0.
+        m = evaluate.compute_metrics_for_smpl(gt_q, gt_j, 0., pq, pj, floor)
+        skip = () if opt.gt_quat else ("root_dist", "root_rot_dist", "head_dist", "head_rot_dist")
+        # (mpjpe_mm keeps the ground truth file's own precision; "metrics" holds what the device computes from float32 tensors)
         rep["mpjpe_mm"] = [mpjpe_mm(gj[i, : gt.shape[0]].cpu(), gt[:t]) for i in range(b)]
+        rep["metrics"] = {k: m[k].tolist() for k in evaluate.METRIC_KEYS + ("single_jpe",) if k not in skip}
     np.savez_compressed(opt.out, **out)
     print(json.dumps(rep), flush=True)
     if dist is not None:
