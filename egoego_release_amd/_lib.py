@@ -183,26 +183,22 @@ def load():
     return lib
 
 
-def check_s1(rc):
-    if rc != 0:
-        raise EgoEgoHipError(f"libegoego_hip stage-1 error {rc}: {load().egoego_s1_last_error().decode()}")
+def _checker(module, last_error):
+    """-> check(rc): raises EgoEgoHipError with the module's own last error on a non-zero return code; check.last_error() reads
+    that text."""
+    def read():
+        return getattr(load(), last_error)().decode()
+
+    def check(rc):
+        if rc != 0:
+            raise EgoEgoHipError(f"libegoego_hip {module}error {rc}: {read()}")
+
+    check.last_error = read
+    return check
 
 
-def check_flow(rc):
-    if rc != 0:
-        raise EgoEgoHipError(f"libegoego_hip flow-CNN error {rc}: {load().egoego_flow_last_error().decode()}")
-
-
-def check_body(rc):
-    if rc != 0:
-        raise EgoEgoHipError(f"libegoego_hip body-model error {rc}: {load().egoego_body_last_error().decode()}")
-
-
-def check_eval(rc):
-    if rc != 0:
-        raise EgoEgoHipError(f"libegoego_hip evaluation error {rc}: {load().egoego_eval_last_error().decode()}")
-
-
-def check(rc):
-    if rc != 0:
-        raise EgoEgoHipError(f"libegoego_hip error {rc}: {load().egoego_last_error().decode()}")
+check = _checker("", "egoego_last_error")
+check_s1 = _checker("stage-1 ", "egoego_s1_last_error")
+check_flow = _checker("flow-CNN ", "egoego_flow_last_error")
+check_body = _checker("body-model ", "egoego_body_last_error")
+check_eval = _checker("evaluation ", "egoego_eval_last_error")

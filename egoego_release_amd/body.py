@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._engine import ContextEngine, EngineCacheMixin
 
 N_JOINTS = _lib.BODY_N_JOINTS
 POSE_FEATS = _lib.BODY_POSE_FEATS
@@ -100,24 +101,18 @@ def regress_joints(J_regressor, v_template, shapedirs):
     return jt.astype(np.float32), np.ascontiguousarray(jsd.astype(np.float32))
 
 
-class BodyEngine:
+class BodyEngine(ContextEngine):
     """One body-model context of libegoego_hip on one GPU; frames run in chunks of `chunk_frames` (0 = the library's default)."""
 
-    def __init__(self, device, chunk_frames=0):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.EgoEgoHipError("the body model needs a cuda (ROCm) device; there is no CPU path")
-        self.dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", self.dev_index)
-        self.chunk_frames = int(chunk_frames)
-        self._ctx = C.c_void_p()
-        _lib.check_body(self.lib.egoego_body_ctx_create(self.dev_index, self.chunk_frames, C.byref(self._ctx)))
-        self._ws = None
-        self.n_verts = self.n_betas = self.n_weights = 0
+    NOUN = "the body model"
+    CREATE, DESTROY, WORKSPACE_BYTES = "egoego_body_ctx_create", "egoego_body_ctx_destroy", "egoego_body_workspace_bytes"
+    CHECK = _lib.check_body
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev_index).cuda_stream)
+    def __init__(self, device, chunk_frames=0):
+        super().__init__(device)
+        self.chunk_frames = int(chunk_frames)
+        self._create(self.dev_index, self.chunk_frames)
+        self.n_verts = self.n_betas = self.n_weights = 0
 
     def load(self, arrays):
         """`arrays`: load_model_arrays' dict (numpy arrays or tensors)."""
@@ -145,15 +140,6 @@ class BodyEngine:
             _lib.check_body(self.lib.egoego_body_load_model(self._ctx, C.byref(m), self._stream()))
         del keep
         self.n_verts, self.n_betas, self.n_weights = m.n_verts, m.n_betas, m.n_weights
-
-    def _workspace(self, N, S):
-        n = self.lib.egoego_body_workspace_bytes(self._ctx, N, S)
-        if n == 0:
-            raise _lib.EgoEgoHipError(self.lib.egoego_body_last_error().decode())
-        if self._ws is None or self._ws.numel() < n + 256:
-            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-        off = (-self._ws.data_ptr()) % 256
-        return self._ws.data_ptr() + off, self._ws.numel() - off
 
     def forward(self, root_orient, pose_body, pose_hand, trans, betas, seq_index, pose_offsets=False):
         """root_orient [N, 3], pose_body [N, 63], pose_hand [N, 90] or None, trans [N, 3], betas [S, n_betas], seq_index [N]
@@ -189,17 +175,6 @@ class BodyEngine:
                 off.data_ptr() if off is not None else None, ws, n, self._stream()))
         return (verts, joints, off) if pose_offsets else (verts, joints)
 
-    def close(self):
-        if getattr(self, "_ctx", None) and self._ctx.value:
-            self.lib.egoego_body_ctx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class BodyOutput:
     """What human_body_prior's BodyModel returns, as far as run_smpl_model reads it."""
@@ -210,13 +185,15 @@ class BodyOutput:
             self.pose_offsets = pose_offsets
 
 
-class BodyModel(nn.Module):
+class BodyModel(EngineCacheMixin, nn.Module):
     """Drop-in for human_body_prior's BodyModel(bm_fname, num_betas) as run_smpl_model uses it, on libegoego_hip.
 
     `bm_fname` is an SMPL-H model.npz (v_template, shapedirs, posedirs, J_regressor, weights, kintree_table, f); `model` a
     mapping with the same arrays instead.  Shapedirs are truncated to `num_betas`.  Any vertex and face count is accepted;
     the model must have 52 joints and a kintree_table whose parents precede their children.  `chunk_frames` bounds the frames
     per pass through the workspace (0 = the library's default)."""
+
+    ENGINE = BodyEngine
 
     def __init__(self, bm_fname=None, num_betas=16, device=None, model=None, chunk_frames=0):
         super().__init__()
@@ -232,29 +209,11 @@ class BodyModel(nn.Module):
         self._engine = None
         self._packed = None
 
-    def to(self, *args, **kwargs):
-        device = torch._C._nn._parse_to(*args, **kwargs)[0]
-        if device is not None:
-            self.device = torch.device(device)
-        super().to(*args, **kwargs)
-        return self
-
     def _params_version(self):
         return tuple((b.data_ptr(), b._version) for b in self.buffers())
 
-    def engine(self):
-        dev = self.device
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        e = self._engine
-        if e is None or e.device != dev or e.chunk_frames != self.chunk_frames:
-            self._engine = BodyEngine(dev, self.chunk_frames)
-            self._packed = None
-        v = self._params_version()
-        if v != self._packed:
-            self._engine.load({k: b for k, b in self.named_buffers()})
-            self._packed = v
-        return self._engine
+    def _engine_state(self):
+        return dict(self.named_buffers())
 
     def forward(self, root_orient=None, pose_body=None, pose_hand=None, betas=None, trans=None, seq_index=None,
                 return_pose_offsets=False, **unused):

@@ -1,35 +1,11 @@
 // flow_cnn.hip — context, weight packing, workspace and the C ABI (include/egoego_hip.h, egoego_flow_*) of the optical-flow
 // ResNet-18 feature extractor (egoego/model/resnet.py = RN).  Kernels: flow_cnn.h.  Nothing here touches another code path.
-#include "../../include/egoego_hip.h"
-
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
 
-#include <string>
-#include <vector>
-
+#include "host_util.h"
 #include "flow_cnn.h"
 
 using namespace fcnn;
-
-static thread_local std::string fl_err;
-static int fl_fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    fl_err = buf;
-    return code;
-}
-#define FL_TRY(expr)                                                                                                   \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-            return fl_fail(EGOEGO_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
-    } while (0)
 
 static constexpr int N_CONV = 20;
 static constexpr int IMG = 224;
@@ -53,47 +29,10 @@ struct FConv {
 struct egoego_flow_ctx {
     int device, chunk;
     bool loaded;
-    std::vector<void*> allocs;
+    DevMem mem;
     FConv conv[N_CONV];
     FConv fc;
 };
-
-static hipStream_t S(void* s) { return (hipStream_t)s; }
-
-static uint16_t bf16_bits(float v) {
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static float bf16_val(uint16_t b) {
-    uint32_t u = (uint32_t)b << 16;
-    float v;
-    memcpy(&v, &u, 4);
-    return v;
-}
-
-static int dev_alloc(egoego_flow_ctx* c, size_t bytes, void** p) {
-    FL_TRY(hipMalloc(p, bytes));
-    c->allocs.push_back(*p);
-    return 0;
-}
-
-static int fetch(const float* d, size_t n, std::vector<float>& h) {
-    if (!d) return fl_fail(EGOEGO_E_INVALID, "a weight pointer is NULL");
-    h.resize(n);
-    FL_TRY(hipMemcpy(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-template <typename T>
-static int upload(egoego_flow_ctx* c, const std::vector<T>& h, const T** out) {
-    void* p;
-    if (int rc = dev_alloc(c, h.size() * sizeof(T), &p)) return rc;
-    FL_TRY(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = (const T*)p;
-    return 0;
-}
 
 // The reference's conv weight (Cout, cin_src, KH, KW) -> [Cout][kh][kw][Cin] (only the first Cin input channels) as hi / lo
 // fragment-tiled planes with K padded to a multiple of 32; scale / shift from the BatchNorm (or the fc's bias with scale 1).
@@ -109,10 +48,7 @@ static int pack_conv(egoego_flow_ctx* c, const float* w, int Cout, int cin_src, 
                 for (int ci = 0; ci < Cin; ++ci) {
                     const float v = tmp[(((size_t)co * cin_src + ci) * KH + kh) * KW + kw];
                     const int k = (kh * KW + kw) * Cin + ci;
-                    const size_t idx = tiled_index(co, k, K16);
-                    const uint16_t h = bf16_bits(v);
-                    hi[idx] = h;
-                    lo[idx] = bf16_bits(v - bf16_val(h));
+                    split_store(hi, lo, tiled_index(co, k, K16), v);
                 }
     std::vector<float> sc(Cout), sh(Cout);
     if (bias) {
@@ -135,19 +71,13 @@ static int pack_conv(egoego_flow_ctx* c, const float* w, int Cout, int cin_src, 
     }
     out.Cin = Cin; out.Cout = Cout; out.KH = KH; out.KW = KW; out.stride = stride; out.pad = pad; out.K16 = K16;
     const uint16_t *dh, *dl;
-    if (int rc = upload(c, hi, &dh)) return rc;
-    if (int rc = upload(c, lo, &dl)) return rc;
-    if (int rc = upload(c, sc, &out.scale)) return rc;
-    if (int rc = upload(c, sh, &out.shift)) return rc;
+    if (int rc = c->mem.upload(hi, &dh)) return rc;
+    if (int rc = c->mem.upload(lo, &dl)) return rc;
+    if (int rc = c->mem.upload(sc, &out.scale)) return rc;
+    if (int rc = c->mem.upload(sh, &out.shift)) return rc;
     out.hi = (const __bf16*)dh;
     out.lo = (const __bf16*)dl;
     return 0;
-}
-
-static void free_weights(egoego_flow_ctx* c) {
-    for (void* p : c->allocs) (void)hipFree(p);
-    c->allocs.clear();
-    c->loaded = false;
 }
 
 static size_t ws_bytes(const egoego_flow_ctx* c, int n) {
@@ -177,21 +107,42 @@ static hipError_t launch_conv(const FConv& cv, const float* x, float* y, const f
 #define FL_LAUNCH(expr)                                                                                                \
     do {                                                                                                               \
         hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) return fl_fail(EGOEGO_E_HIP, "flow-CNN launch failed: %s (%s:%d)", hipGetErrorString(e_),   \
-                                             __FILE__, __LINE__);                                                      \
+        if (e_ != hipSuccess)                                                                                          \
+            return fail(EGOEGO_E_HIP, "flow-CNN launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+static int pack_weights(egoego_flow_ctx* c, const egoego_flow_weights* w) {
+    int i = 0;
+    auto conv = [&](int cin_src, int cin, int cout, int k, int stride, int pad) -> int {
+        const int j = i++;
+        return pack_conv(c, w->conv_w[j], cout, cin_src, cin, k, k, stride, pad, w->bn_w[j], w->bn_b[j], w->bn_mean[j],
+                         w->bn_var[j], nullptr, c->conv[j]);
+    };
+    if (int r = conv(3, 2, 64, 7, 2, 3)) return r;  // the zero third input channel is dropped
+    int cin = 64;
+    for (int l = 0; l < 4; ++l) {
+        const int cout = 64 << l;
+        for (int b = 0; b < 2; ++b) {
+            const int stride = (l > 0 && b == 0) ? 2 : 1;
+            if (int r = conv(b == 0 ? cin : cout, b == 0 ? cin : cout, cout, 3, stride, 1)) return r;
+            if (int r = conv(cout, cout, cout, 3, 1, 1)) return r;
+            if (l > 0 && b == 0)
+                if (int r = conv(cin, cin, cout, 1, 2, 0)) return r;
+        }
+        cin = cout;
+    }
+    return pack_conv(c, w->fc_w, FEAT, FEAT, FEAT, 1, 1, 1, 0, nullptr, nullptr, nullptr, nullptr, w->fc_b, c->fc);
+}
 
 extern "C" {
 
-const char* egoego_flow_last_error(void) { return fl_err.c_str(); }
+const char* egoego_flow_last_error(void) { return last_err.c_str(); }
 
 int egoego_flow_ctx_create(int device, int chunk_frames, egoego_flow_ctx** out) {
-    if (!out) return fl_fail(EGOEGO_E_INVALID, "NULL argument");
+    if (!out) return fail(EGOEGO_E_INVALID, "NULL argument");
     *out = nullptr;
-    if (chunk_frames < 0 || chunk_frames > 4096) return fl_fail(EGOEGO_E_INVALID, "chunk_frames %d: 0..4096 accepted", chunk_frames);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return fl_fail(EGOEGO_E_INVALID, "device %d not available", device);
+    if (chunk_frames < 0 || chunk_frames > 4096) return fail(EGOEGO_E_INVALID, "chunk_frames %d: 0..4096 accepted", chunk_frames);
+    if (int rc = check_device(device)) return rc;
     egoego_flow_ctx* c = new egoego_flow_ctx();
     c->device = device;
     c->chunk = chunk_frames ? chunk_frames : DEFAULT_CHUNK;
@@ -200,55 +151,24 @@ int egoego_flow_ctx_create(int device, int chunk_frames, egoego_flow_ctx** out) 
     return 0;
 }
 
-void egoego_flow_ctx_destroy(egoego_flow_ctx* c) {
-    if (!c) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(c->device);
-    free_weights(c);
-    (void)hipSetDevice(prev);
-    delete c;
-}
+void egoego_flow_ctx_destroy(egoego_flow_ctx* c) { destroy_ctx(c); }
 
 int egoego_flow_load_weights(egoego_flow_ctx* c, const egoego_flow_weights* w, void* stream) {
-    if (!c || !w) return fl_fail(EGOEGO_E_INVALID, "NULL argument");
-    int prev = 0;
-    FL_TRY(hipGetDevice(&prev));
-    FL_TRY(hipSetDevice(c->device));
-    FL_TRY(hipStreamSynchronize(S(stream)));  // the caller's tensors are written on its stream; old weights may still be read
-    free_weights(c);
-    auto run = [&]() -> int {
-        int i = 0;
-        auto conv = [&](int cin_src, int cin, int cout, int k, int stride, int pad) -> int {
-            const int j = i++;
-            return pack_conv(c, w->conv_w[j], cout, cin_src, cin, k, k, stride, pad, w->bn_w[j], w->bn_b[j], w->bn_mean[j],
-                             w->bn_var[j], nullptr, c->conv[j]);
-        };
-        if (int r = conv(3, 2, 64, 7, 2, 3)) return r;  // the zero third input channel is dropped
-        int cin = 64;
-        for (int l = 0; l < 4; ++l) {
-            const int cout = 64 << l;
-            for (int b = 0; b < 2; ++b) {
-                const int stride = (l > 0 && b == 0) ? 2 : 1;
-                if (int r = conv(b == 0 ? cin : cout, b == 0 ? cin : cout, cout, 3, stride, 1)) return r;
-                if (int r = conv(cout, cout, cout, 3, 1, 1)) return r;
-                if (l > 0 && b == 0)
-                    if (int r = conv(cin, cin, cout, 1, 2, 0)) return r;
-            }
-            cin = cout;
-        }
-        return pack_conv(c, w->fc_w, FEAT, FEAT, FEAT, 1, 1, 1, 0, nullptr, nullptr, nullptr, nullptr, w->fc_b, c->fc);
-    };
-    const int rc = run();
+    if (!c || !w) return fail(EGOEGO_E_INVALID, "NULL argument");
+    DeviceGuard dev;
+    if (int rc = dev.enter(c->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(as_stream(stream)));  // the caller's tensors are written on its stream; old weights may still be read
+    c->mem.free_all();
+    c->loaded = false;
+    const int rc = pack_weights(c, w);
     if (rc == 0) c->loaded = true;
-    else free_weights(c);
-    (void)hipSetDevice(prev);
+    else c->mem.free_all();
     return rc;
 }
 
 size_t egoego_flow_workspace_bytes(const egoego_flow_ctx* c, int n_frames) {
     if (!c || n_frames < 1) {
-        fl_fail(EGOEGO_E_INVALID, "n_frames must be >= 1");
+        fail(EGOEGO_E_INVALID, "n_frames must be >= 1");
         return 0;
     }
     return ws_bytes(c, n_frames);
@@ -256,19 +176,17 @@ size_t egoego_flow_workspace_bytes(const egoego_flow_ctx* c, int n_frames) {
 
 int egoego_flow_features(egoego_flow_ctx* c, const float* d_flow, int N, float* d_out, float* d_stages, void* d_ws, size_t ws_n,
                          void* stream) {
-    if (!c || !d_flow || !d_out) return fl_fail(EGOEGO_E_INVALID, "NULL argument");
-    if (!c->loaded) return fl_fail(EGOEGO_E_STATE, "weights not loaded");
-    if (N < 1) return fl_fail(EGOEGO_E_INVALID, "n_frames must be >= 1");
-    if (!d_ws || ((uintptr_t)d_ws & 255) || ws_n < ws_bytes(c, N))
-        return fl_fail(EGOEGO_E_WORKSPACE, "workspace: %zu bytes at %p, need %zu (256-byte aligned)", ws_n, d_ws, ws_bytes(c, N));
+    if (!c || !d_flow || !d_out) return fail(EGOEGO_E_INVALID, "NULL argument");
+    if (!c->loaded) return fail(EGOEGO_E_STATE, "weights not loaded");
+    if (N < 1) return fail(EGOEGO_E_INVALID, "n_frames must be >= 1");
+    if (int rc = check_workspace(d_ws, ws_n, ws_bytes(c, N))) return rc;
     if (((uintptr_t)d_flow & 7) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_stages & 15))
-        return fl_fail(EGOEGO_E_INVALID, "d_flow must be 8-byte aligned, d_out and d_stages 16-byte aligned");
-    int prev = 0;
-    FL_TRY(hipGetDevice(&prev));
-    FL_TRY(hipSetDevice(c->device));
+        return fail(EGOEGO_E_INVALID, "d_flow must be 8-byte aligned, d_out and d_stages 16-byte aligned");
+    DeviceGuard dev;
+    if (int rc = dev.enter(c->device)) return rc;
     // every launch below is checked on its own; an error some earlier, unrelated call left pending is not ours to report
     (void)hipGetLastError();
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const int chunk = N < c->chunk ? N : c->chunk;
     float* ws = (float*)d_ws;
     float* buf[N_BUF];
@@ -279,13 +197,13 @@ int egoego_flow_features(egoego_flow_ctx* c, const float* d_flow, int N, float* 
         stage_off[i] = off;
         off += (size_t)N * STAGE_HW[i] * STAGE_HW[i] * STAGE_C[i];
     }
-    // one chunk of F frames from frame f0; any failure returns here, and the device is restored below in one place
-    auto run_chunk = [&](int f0, int F) -> int {
+    for (int f0 = 0; f0 < N; f0 += chunk) {  // one chunk of F frames from frame f0
+        const int F = N - f0 < chunk ? N - f0 : chunk;
         auto stage = [&](int i, const float* src) -> int {
             if (!d_stages) return 0;
             const size_t per = (size_t)STAGE_HW[i] * STAGE_HW[i] * STAGE_C[i];
-            FL_TRY(hipMemcpyAsync(d_stages + stage_off[i] + (size_t)f0 * per, src, (size_t)F * per * sizeof(float),
-                                  hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(d_stages + stage_off[i] + (size_t)f0 * per, src, (size_t)F * per * sizeof(float),
+                                   hipMemcpyDeviceToDevice, s));
             return 0;
         };
         // stem: conv1 + bn1 + ReLU into buffers 0-3 (one [F][112][112][64] array), max-pool into buffer 4
@@ -327,12 +245,8 @@ int egoego_flow_features(egoego_flow_ctx* c, const float* d_flow, int N, float* 
             FL_LAUNCH(hipGetLastError());
         }
         FL_LAUNCH(launch_conv(c->fc, pooled, d_out + (size_t)f0 * FEAT, nullptr, F, 1, 1, false, false, s));
-        return 0;
-    };
-    int rc = 0;
-    for (int f0 = 0; f0 < N && rc == 0; f0 += chunk) rc = run_chunk(f0, N - f0 < chunk ? N - f0 : chunk);
-    (void)hipSetDevice(prev);
-    return rc;
+    }
+    return 0;
 }
 
 }  // extern "C"

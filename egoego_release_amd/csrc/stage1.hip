@@ -1,35 +1,11 @@
 // stage1.hip — context, weight packing, workspace and the C ABI (include/egoego_hip.h, egoego_s1_*) of the stage-1 head-pose
 // estimators.  Kernels: stage1.h.  Nothing here touches a stage-2 code path.
-#include "../../include/egoego_hip.h"
-
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
 
-#include <string>
-#include <vector>
-
+#include "host_util.h"
 #include "stage1.h"
 
 using namespace s1;
-
-static thread_local std::string s1_err;
-static int s1_fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    s1_err = buf;
-    return code;
-}
-#define S1_TRY(expr)                                                                                                   \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-            return s1_fail(EGOEGO_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
-    } while (0)
 
 static constexpr int MAX_LAYERS = 8;
 static constexpr int MAX_HEAD = 4;  // linears per head (HeadNet: 3 hidden + fc)
@@ -43,7 +19,7 @@ struct egoego_s1_ctx {
     egoego_s1_config cfg;
     int device, Lp;
     bool loaded, tail_attr;
-    std::vector<void*> allocs;
+    DevMem mem;
     Lin embed;
     float* pos;
     S1Layer layers[MAX_LAYERS];
@@ -53,34 +29,6 @@ struct egoego_s1_ctx {
     int n_lin;             // linears per head
     int n_heads;
 };
-
-static hipStream_t S(void* s) { return (hipStream_t)s; }
-
-static uint16_t bf16_bits(float v) {
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static float bf16_val(uint16_t b) {
-    uint32_t u = (uint32_t)b << 16;
-    float v;
-    memcpy(&v, &u, 4);
-    return v;
-}
-
-static int dev_alloc(egoego_s1_ctx* c, size_t bytes, void** p) {
-    S1_TRY(hipMalloc(p, bytes));
-    c->allocs.push_back(*p);
-    return 0;
-}
-
-static int fetch(const float* d, size_t n, std::vector<float>& h) {
-    if (!d) return s1_fail(EGOEGO_E_INVALID, "a weight pointer is NULL");
-    h.resize(n);
-    S1_TRY(hipMemcpy(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
 
 // Pack the rows of `parts` (each [rows][K] fp32 on the device, stacked) into hi / lo fragment-tiled planes.
 static int pack_lin(egoego_s1_ctx* c, const std::vector<std::pair<const float*, int>>& w, const std::vector<const float*>& b, int K,
@@ -95,66 +43,78 @@ static int pack_lin(egoego_s1_ctx* c, const std::vector<std::pair<const float*, 
         const int rows = w[i].second;
         if (int rc = fetch(w[i].first, (size_t)rows * K, tmp)) return rc;
         for (int r = 0; r < rows; ++r)
-            for (int k = 0; k < K; ++k) {
-                const float v = tmp[(size_t)r * K + k];
-                const uint16_t h = bf16_bits(v);
-                const size_t idx = tiled_index(r0 + r, k, K16);
-                hi[idx] = h;
-                lo[idx] = bf16_bits(v - bf16_val(h));
-            }
+            for (int k = 0; k < K; ++k)
+                split_store(hi, lo, tiled_index(r0 + r, k, K16), tmp[(size_t)r * K + k]);
         if (int rc = fetch(b[i], rows, tmp)) return rc;
         memcpy(bias.data() + r0, tmp.data(), rows * sizeof(float));
         r0 += rows;
     }
-    void *dh, *dl, *db;
-    if (int rc = dev_alloc(c, hi.size() * 2, &dh)) return rc;
-    if (int rc = dev_alloc(c, lo.size() * 2, &dl)) return rc;
-    if (int rc = dev_alloc(c, bias.size() * 4, &db)) return rc;
-    S1_TRY(hipMemcpy(dh, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
-    S1_TRY(hipMemcpy(dl, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
-    S1_TRY(hipMemcpy(db, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+    const uint16_t *dh, *dl;
+    if (int rc = c->mem.upload(hi, &dh)) return rc;
+    if (int rc = c->mem.upload(lo, &dl)) return rc;
+    if (int rc = c->mem.upload(bias, &out.b)) return rc;
     out.hi = (const __bf16*)dh;
     out.lo = (const __bf16*)dl;
-    out.b = (const float*)db;
     out.N = N;
     out.K16 = K16;
     return 0;
 }
 
-static int copy_vec(egoego_s1_ctx* c, const float* d, size_t n, float** out) {
-    if (!d) return s1_fail(EGOEGO_E_INVALID, "a weight pointer is NULL");
-    void* p;
-    if (int rc = dev_alloc(c, n * 4, &p)) return rc;
-    S1_TRY(hipMemcpy(p, d, n * 4, hipMemcpyDeviceToDevice));
-    *out = (float*)p;
+static int pack_weights(egoego_s1_ctx* c, const egoego_s1_weights* w) {
+    const egoego_s1_config& g = c->cfg;
+    if (int r = pack_lin(c, {{w->start_conv_w, DM}}, {w->start_conv_b}, g.d_feats, c->embed)) return r;
+    if (int r = c->mem.copy_dev(w->position_vec, (size_t)(g.window + 1) * DM, &c->pos)) return r;
+    for (int i = 0; i < g.n_dec_layers; ++i) {
+        const egoego_layer_weights& L = w->layers[i];
+        S1Layer& d = c->layers[i];
+        if (int r = pack_lin(c, {{L.w_q, HD}, {L.w_k, HD}, {L.w_v, HD}}, {L.b_q, L.b_k, L.b_v}, DM, d.qkv)) return r;
+        if (int r = pack_lin(c, {{L.w_fc, DM}}, {L.b_fc}, HD, d.fc)) return r;
+        if (int r = pack_lin(c, {{L.w_1, DM}}, {L.b_1}, DM, d.w1)) return r;
+        if (int r = pack_lin(c, {{L.w_2, DM}}, {L.b_2}, DM, d.w2)) return r;
+        if (int r = c->mem.copy_dev(L.ln1_g, DM, &d.ln1_g)) return r;
+        if (int r = c->mem.copy_dev(L.ln1_b, DM, &d.ln1_b)) return r;
+        if (int r = c->mem.copy_dev(L.ln2_g, DM, &d.ln2_g)) return r;
+        if (int r = c->mem.copy_dev(L.ln2_b, DM, &d.ln2_b)) return r;
+    }
+    if (g.kind == EGOEGO_S1_HEADNET) {
+        // va: 256 -> 1024 -> 512 -> 256 -> 3; dist: 256 -> 1024 -> 512 -> 256 -> 1
+        c->n_heads = 2;
+        c->n_lin = 4;
+        if (int r = pack_lin(c, {{w->head_w[0], 1024}, {w->head_w[4], 1024}}, {w->head_b[0], w->head_b[4]}, DM, c->h0)) return r;
+        const int dims[4][2] = {{1024, 256}, {512, 1024}, {256, 512}, {0, 256}};
+        for (int h = 0; h < 2; ++h)
+            for (int i = 1; i < 4; ++i) {
+                const int N = i < 3 ? dims[i][0] : (h == 0 ? 3 : 1);
+                if (int r = pack_lin(c, {{w->head_w[4 * h + i], N}}, {w->head_b[4 * h + i]}, dims[i][1], c->hid[h][i - 1])) return r;
+            }
+    } else {
+        // normal: 256 -> 512 -> 256 -> 3 on token 0
+        c->n_heads = 1;
+        c->n_lin = 3;
+        if (int r = pack_lin(c, {{w->head_w[0], 512}}, {w->head_b[0]}, DM, c->h0)) return r;
+        if (int r = pack_lin(c, {{w->head_w[1], 256}}, {w->head_b[1]}, 512, c->hid[0][0])) return r;
+        if (int r = pack_lin(c, {{w->head_w[2], 3}}, {w->head_b[2]}, 256, c->hid[0][1])) return r;
+    }
     return 0;
-}
-
-static void free_weights(egoego_s1_ctx* c) {
-    for (void* p : c->allocs) (void)hipFree(p);
-    c->allocs.clear();
-    c->loaded = false;
 }
 
 extern "C" {
 
-const char* egoego_s1_last_error(void) { return s1_err.c_str(); }
+const char* egoego_s1_last_error(void) { return last_err.c_str(); }
 
 int egoego_s1_ctx_create(const egoego_s1_config* cfg, int device, egoego_s1_ctx** out) {
-    if (!cfg || !out) return s1_fail(EGOEGO_E_INVALID, "NULL argument");
+    if (!cfg || !out) return fail(EGOEGO_E_INVALID, "NULL argument");
     *out = nullptr;
-    if (cfg->kind != EGOEGO_S1_HEADNET && cfg->kind != EGOEGO_S1_GRAVITYNET) return s1_fail(EGOEGO_E_INVALID, "unknown kind %d", cfg->kind);
-    if (cfg->d_model != DM) return s1_fail(EGOEGO_E_INVALID, "d_model %d: stage 1 supports 256 only", cfg->d_model);
+    if (cfg->kind != EGOEGO_S1_HEADNET && cfg->kind != EGOEGO_S1_GRAVITYNET) return fail(EGOEGO_E_INVALID, "unknown kind %d", cfg->kind);
+    if (cfg->d_model != DM) return fail(EGOEGO_E_INVALID, "d_model %d: stage 1 supports 256 only", cfg->d_model);
     if (cfg->n_head * cfg->d_k != HD || cfg->n_head * cfg->d_v != HD || cfg->n_head != NH)
-        return s1_fail(EGOEGO_E_INVALID, "n_head %d, d_k %d, d_v %d: stage 1 supports n_head 4, d_k = d_v = 256 only", cfg->n_head,
+        return fail(EGOEGO_E_INVALID, "n_head %d, d_k %d, d_v %d: stage 1 supports n_head 4, d_k = d_v = 256 only", cfg->n_head,
                        cfg->d_k, cfg->d_v);
     if (cfg->n_dec_layers < 1 || cfg->n_dec_layers > MAX_LAYERS)
-        return s1_fail(EGOEGO_E_INVALID, "n_dec_layers %d: 1..%d supported", cfg->n_dec_layers, MAX_LAYERS);
-    if (cfg->window < 1 || cfg->window > 128) return s1_fail(EGOEGO_E_INVALID, "window %d: 1..128 supported", cfg->window);
-    if (cfg->d_feats < 1 || cfg->d_feats > 1024) return s1_fail(EGOEGO_E_INVALID, "d_feats %d: 1..1024 supported", cfg->d_feats);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return s1_fail(EGOEGO_E_INVALID, "device %d not available", device);
+        return fail(EGOEGO_E_INVALID, "n_dec_layers %d: 1..%d supported", cfg->n_dec_layers, MAX_LAYERS);
+    if (cfg->window < 1 || cfg->window > 128) return fail(EGOEGO_E_INVALID, "window %d: 1..128 supported", cfg->window);
+    if (cfg->d_feats < 1 || cfg->d_feats > 1024) return fail(EGOEGO_E_INVALID, "d_feats %d: 1..1024 supported", cfg->d_feats);
+    if (int rc = check_device(device)) return rc;
     egoego_s1_ctx* c = new egoego_s1_ctx();
     c->cfg = *cfg;
     c->device = device;
@@ -165,65 +125,18 @@ int egoego_s1_ctx_create(const egoego_s1_config* cfg, int device, egoego_s1_ctx*
     return 0;
 }
 
-void egoego_s1_ctx_destroy(egoego_s1_ctx* c) {
-    if (!c) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(c->device);
-    free_weights(c);
-    (void)hipSetDevice(prev);
-    delete c;
-}
+void egoego_s1_ctx_destroy(egoego_s1_ctx* c) { destroy_ctx(c); }
 
 int egoego_s1_load_weights(egoego_s1_ctx* c, const egoego_s1_weights* w, void* stream) {
-    if (!c || !w || !w->layers) return s1_fail(EGOEGO_E_INVALID, "NULL argument");
-    int prev = 0;
-    S1_TRY(hipGetDevice(&prev));
-    S1_TRY(hipSetDevice(c->device));
-    S1_TRY(hipStreamSynchronize(S(stream)));  // the caller's tensors are written on its stream; old weights may still be read
-    free_weights(c);
-    const egoego_s1_config& g = c->cfg;
-    int rc = 0;
-    auto run = [&]() -> int {
-        if (int r = pack_lin(c, {{w->start_conv_w, DM}}, {w->start_conv_b}, g.d_feats, c->embed)) return r;
-        if (int r = copy_vec(c, w->position_vec, (size_t)(g.window + 1) * DM, &c->pos)) return r;
-        for (int i = 0; i < g.n_dec_layers; ++i) {
-            const egoego_layer_weights& L = w->layers[i];
-            S1Layer& d = c->layers[i];
-            if (int r = pack_lin(c, {{L.w_q, HD}, {L.w_k, HD}, {L.w_v, HD}}, {L.b_q, L.b_k, L.b_v}, DM, d.qkv)) return r;
-            if (int r = pack_lin(c, {{L.w_fc, DM}}, {L.b_fc}, HD, d.fc)) return r;
-            if (int r = pack_lin(c, {{L.w_1, DM}}, {L.b_1}, DM, d.w1)) return r;
-            if (int r = pack_lin(c, {{L.w_2, DM}}, {L.b_2}, DM, d.w2)) return r;
-            if (int r = copy_vec(c, L.ln1_g, DM, &d.ln1_g)) return r;
-            if (int r = copy_vec(c, L.ln1_b, DM, &d.ln1_b)) return r;
-            if (int r = copy_vec(c, L.ln2_g, DM, &d.ln2_g)) return r;
-            if (int r = copy_vec(c, L.ln2_b, DM, &d.ln2_b)) return r;
-        }
-        if (g.kind == EGOEGO_S1_HEADNET) {
-            // va: 256 -> 1024 -> 512 -> 256 -> 3; dist: 256 -> 1024 -> 512 -> 256 -> 1
-            c->n_heads = 2;
-            c->n_lin = 4;
-            if (int r = pack_lin(c, {{w->head_w[0], 1024}, {w->head_w[4], 1024}}, {w->head_b[0], w->head_b[4]}, DM, c->h0)) return r;
-            const int dims[4][2] = {{1024, 256}, {512, 1024}, {256, 512}, {0, 256}};
-            for (int h = 0; h < 2; ++h)
-                for (int i = 1; i < 4; ++i) {
-                    const int N = i < 3 ? dims[i][0] : (h == 0 ? 3 : 1);
-                    if (int r = pack_lin(c, {{w->head_w[4 * h + i], N}}, {w->head_b[4 * h + i]}, dims[i][1], c->hid[h][i - 1])) return r;
-                }
-        } else {
-            // normal: 256 -> 512 -> 256 -> 3 on token 0
-            c->n_heads = 1;
-            c->n_lin = 3;
-            if (int r = pack_lin(c, {{w->head_w[0], 512}}, {w->head_b[0]}, DM, c->h0)) return r;
-            if (int r = pack_lin(c, {{w->head_w[1], 256}}, {w->head_b[1]}, 512, c->hid[0][0])) return r;
-            if (int r = pack_lin(c, {{w->head_w[2], 3}}, {w->head_b[2]}, 256, c->hid[0][1])) return r;
-        }
-        return 0;
-    };
-    rc = run();
+    if (!c || !w || !w->layers) return fail(EGOEGO_E_INVALID, "NULL argument");
+    DeviceGuard dev;
+    if (int rc = dev.enter(c->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(as_stream(stream)));  // the caller's tensors are written on its stream; old weights may still be read
+    c->mem.free_all();
+    c->loaded = false;
+    const int rc = pack_weights(c, w);
     if (rc == 0) c->loaded = true;
-    else free_weights(c);
-    (void)hipSetDevice(prev);
+    else c->mem.free_all();
     return rc;
 }
 
@@ -235,11 +148,11 @@ static size_t ws_bytes(const egoego_s1_ctx* c, int W) {
 
 size_t egoego_s1_workspace_bytes(const egoego_s1_ctx* c, int n_windows) {
     if (!c || n_windows < 1) {
-        s1_fail(EGOEGO_E_INVALID, "n_windows must be >= 1");
+        fail(EGOEGO_E_INVALID, "n_windows must be >= 1");
         return 0;
     }
     if ((size_t)n_windows * c->Lp > (1u << 22)) {
-        s1_fail(EGOEGO_E_INVALID, "%d windows: more than 2^22 rows per call", n_windows);
+        fail(EGOEGO_E_INVALID, "%d windows: more than 2^22 rows per call", n_windows);
         return 0;
     }
     return ws_bytes(c, n_windows);
@@ -265,17 +178,15 @@ static void launch_linear(const float* A, long lda, int a_goff, int K, float* ou
 
 int egoego_s1_encode(egoego_s1_ctx* c, const float* d_feats, const int32_t* d_valid, int W, float* d_out, float* d_layers,
                      void* d_ws, size_t ws_n, void* stream) {
-    if (!c || !d_feats || !d_valid || !d_out) return s1_fail(EGOEGO_E_INVALID, "NULL argument");
-    if (!c->loaded) return s1_fail(EGOEGO_E_STATE, "weights not loaded");
-    if (W < 1) return s1_fail(EGOEGO_E_INVALID, "n_windows must be >= 1");
-    if ((size_t)W * c->Lp > (1u << 22)) return s1_fail(EGOEGO_E_INVALID, "%d windows: more than 2^22 rows per call", W);
-    if (!d_ws || ((uintptr_t)d_ws & 255) || ws_n < ws_bytes(c, W))
-        return s1_fail(EGOEGO_E_WORKSPACE, "workspace: %zu bytes at %p, need %zu (256-byte aligned)", ws_n, d_ws, ws_bytes(c, W));
-    int prev = 0;
-    S1_TRY(hipGetDevice(&prev));
-    S1_TRY(hipSetDevice(c->device));
+    if (!c || !d_feats || !d_valid || !d_out) return fail(EGOEGO_E_INVALID, "NULL argument");
+    if (!c->loaded) return fail(EGOEGO_E_STATE, "weights not loaded");
+    if (W < 1) return fail(EGOEGO_E_INVALID, "n_windows must be >= 1");
+    if ((size_t)W * c->Lp > (1u << 22)) return fail(EGOEGO_E_INVALID, "%d windows: more than 2^22 rows per call", W);
+    if (int rc = check_workspace(d_ws, ws_n, ws_bytes(c, W))) return rc;
+    DeviceGuard dev;
+    if (int rc = dev.enter(c->device)) return rc;
     const egoego_s1_config& g = c->cfg;
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const int Lp = c->Lp, R = W * Lp;
     float* X = (float*)d_ws;
     float* QKV = X + (size_t)R * DM;
@@ -291,10 +202,7 @@ int egoego_s1_encode(egoego_s1_ctx* c, const float* d_feats, const int32_t* d_va
     if (!c->tail_attr) {  // 65 KiB of dynamic LDS: opt in once (the context lives on one device)
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(s1_tail_kernel),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_smem);
-        if (e != hipSuccess) {
-            (void)hipSetDevice(prev);
-            return s1_fail(EGOEGO_E_HIP, "hipFuncSetAttribute(s1_tail_kernel) failed: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(EGOEGO_E_HIP, "hipFuncSetAttribute(s1_tail_kernel) failed: %s", hipGetErrorString(e));
         c->tail_attr = true;
     }
     for (int l = 0; l < g.n_dec_layers; ++l) {
@@ -321,20 +229,19 @@ int egoego_s1_encode(egoego_s1_ctx* c, const float* d_feats, const int32_t* d_va
         launch_linear(H2, 256, 0, 256, d_out, 3, 0, &c->hid[0][1], 1, W, false, 0, 0, s);
     }
     const hipError_t e = hipGetLastError();
-    (void)hipSetDevice(prev);
-    if (e != hipSuccess) return s1_fail(EGOEGO_E_HIP, "stage-1 launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(EGOEGO_E_HIP, "stage-1 launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 
 int egoego_s1_gravity_features(const float* d_rot, const float* d_trans, const int32_t* d_len, int Sn, int Lmax, int window,
                                float* d_feats, int32_t* d_valid, void* stream) {
     if (!d_rot || !d_trans || !d_len || !d_feats || !d_valid || Sn < 1 || Lmax < 1 || window < 1)
-        return s1_fail(EGOEGO_E_INVALID, "bad argument");
+        return fail(EGOEGO_E_INVALID, "bad argument");
     const int n = Sn * window;
-    s1_gravity_features_kernel<<<(n + 255) / 256, 256, 0, S(stream)>>>(d_rot, d_trans, (const int*)d_len, Lmax, window, d_feats,
-                                                                       (int*)d_valid, Sn);
+    s1_gravity_features_kernel<<<(n + 255) / 256, 256, 0, as_stream(stream)>>>(d_rot, d_trans, (const int*)d_len, Lmax, window,
+                                                                               d_feats, (int*)d_valid, Sn);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return s1_fail(EGOEGO_E_HIP, "launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(EGOEGO_E_HIP, "launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 
@@ -343,22 +250,23 @@ int egoego_s1_integrate(const float* d_heads, int window, const int32_t* d_T, co
                         double* d_trans, double* d_scale, void* stream) {
     if (!d_heads || !d_T || !d_win0 || !d_q0 || !d_slam || !d_len || !d_quat || !d_trans || !d_scale || Sn < 1 || window < 1 ||
         Lmax < 1 || Qmax < 1)
-        return s1_fail(EGOEGO_E_INVALID, "bad argument");
-    s1_integrate_kernel<<<(Sn + 63) / 64, 64, 0, S(stream)>>>(d_heads, window, (const int*)d_T, (const int*)d_win0, d_q0, d_slam,
-                                                              (const int*)d_len, Lmax, Qmax, dist_scale, d_quat, d_trans, d_scale, Sn);
+        return fail(EGOEGO_E_INVALID, "bad argument");
+    s1_integrate_kernel<<<(Sn + 63) / 64, 64, 0, as_stream(stream)>>>(d_heads, window, (const int*)d_T, (const int*)d_win0, d_q0,
+                                                                      d_slam, (const int*)d_len, Lmax, Qmax, dist_scale, d_quat,
+                                                                      d_trans, d_scale, Sn);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return s1_fail(EGOEGO_E_HIP, "launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(EGOEGO_E_HIP, "launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 
 int egoego_s1_gravity_apply(const float* d_rot, const float* d_trans, const int32_t* d_len, int Sn, int Lmax, const double* d_Rn,
                             const double* d_scale, const double* d_Ralign, const double* d_origin, double* d_pose, void* stream) {
     if (!d_rot || !d_trans || !d_len || !d_Rn || !d_scale || !d_Ralign || !d_origin || !d_pose || Sn < 1 || Lmax < 1)
-        return s1_fail(EGOEGO_E_INVALID, "bad argument");
-    s1_gravity_apply_kernel<<<(Sn + 63) / 64, 64, 0, S(stream)>>>(d_rot, d_trans, (const int*)d_len, Lmax, d_Rn, d_scale, d_Ralign,
-                                                                  d_origin, d_pose, Sn);
+        return fail(EGOEGO_E_INVALID, "bad argument");
+    s1_gravity_apply_kernel<<<(Sn + 63) / 64, 64, 0, as_stream(stream)>>>(d_rot, d_trans, (const int*)d_len, Lmax, d_Rn, d_scale,
+                                                                          d_Ralign, d_origin, d_pose, Sn);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return s1_fail(EGOEGO_E_HIP, "launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(EGOEGO_E_HIP, "launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -25,6 +25,7 @@ import torch
 from torch import nn
 
 from . import _lib, rotations
+from ._engine import ContextEngine, EngineCacheMixin
 from .synthetic import FLOW_FEATS, FLOW_IMG, Stage1Config, flow_cnn_convs, make_flow_cnn_weights, make_stage1_weights
 
 MAX_WINDOW = 128
@@ -60,26 +61,20 @@ def _check_cfg(cfg, input_of_feats=True):
         raise ValueError(f"stage-1 n_dec_layers {cfg.n_dec_layers}: 1..8 supported")
 
 
-class Stage1Engine:
+class Stage1Engine(ContextEngine):
     """One stage-1 context of libegoego_hip on one GPU."""
+
+    NOUN = "stage 1"
+    CREATE, DESTROY, WORKSPACE_BYTES = "egoego_s1_ctx_create", "egoego_s1_ctx_destroy", "egoego_s1_workspace_bytes"
+    CHECK = _lib.check_s1
 
     def __init__(self, cfg, device):
         _check_cfg(cfg)
-        self.lib = _lib.load()
+        super().__init__(device)
         self.cfg = cfg
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.EgoEgoHipError("stage 1 needs a cuda (ROCm) device; there is no CPU path")
-        self.dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", self.dev_index)
         kind = _lib.S1_HEADNET if cfg.kind == "headnet" else _lib.S1_GRAVITYNET
         c = _lib.S1Config(kind, cfg.d_feats, cfg.d_model, cfg.n_head, cfg.n_dec_layers, cfg.d_k, cfg.d_v, cfg.window)
-        self._ctx = C.c_void_p()
-        _lib.check_s1(self.lib.egoego_s1_ctx_create(C.byref(c), self.dev_index, C.byref(self._ctx)))
-        self._ws = None
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev_index).cuda_stream)
+        self._create(C.byref(c), self.dev_index)
 
     def load(self, sd, prefix=""):
         keep = []
@@ -117,15 +112,6 @@ class Stage1Engine:
             _lib.check_s1(self.lib.egoego_s1_load_weights(self._ctx, C.byref(w), self._stream()))
         del keep
 
-    def _workspace(self, W):
-        n = self.lib.egoego_s1_workspace_bytes(self._ctx, W)
-        if n == 0:
-            raise _lib.EgoEgoHipError(self.lib.egoego_s1_last_error().decode())
-        if self._ws is None or self._ws.numel() < n + 256:
-            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-        off = (-self._ws.data_ptr()) % 256
-        return self._ws.data_ptr() + off, self._ws.numel() - off
-
     def encode(self, feats, valid, layers=False):
         """feats [W, window, d_feats] fp32 cuda, valid int32 [W] -> heads ([W, window, 4] | [W, 3]) (+ [L, W, window, 256])."""
         cfg = self.cfg
@@ -141,17 +127,6 @@ class Stage1Engine:
             _lib.check_s1(self.lib.egoego_s1_encode(self._ctx, feats.data_ptr(), valid.data_ptr(), W, out.data_ptr(),
                                                     dbg.data_ptr() if dbg is not None else None, ws, n, self._stream()))
         return (out, dbg) if layers else out
-
-    def close(self):
-        if getattr(self, "_ctx", None) and self._ctx.value:
-            self.lib.egoego_s1_ctx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------------------------------ parameter containers (reference names)
@@ -311,26 +286,19 @@ class HeadFormer(_Stage1Module):
 
 
 # ------------------------------------------------------------------------------------------ the optical-flow CNN (RN)
-class FlowCNNEngine:
+class FlowCNNEngine(ContextEngine):
     """One flow-CNN context of libegoego_hip on one GPU; frames run in chunks of `chunk_frames` (0 = the library's default)."""
 
+    NOUN = "the flow CNN"
+    CREATE, DESTROY, WORKSPACE_BYTES = "egoego_flow_ctx_create", "egoego_flow_ctx_destroy", "egoego_flow_workspace_bytes"
+    CHECK = _lib.check_flow
     N_STAGES = 5
     STAGE_SHAPES = [(56, 56, 64), (56, 56, 64), (28, 28, 128), (14, 14, 256), (7, 7, 512)]
 
     def __init__(self, device, chunk_frames=0):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.EgoEgoHipError("the flow CNN needs a cuda (ROCm) device; there is no CPU path")
-        self.dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", self.dev_index)
+        super().__init__(device)
         self.chunk_frames = int(chunk_frames)
-        self._ctx = C.c_void_p()
-        _lib.check_flow(self.lib.egoego_flow_ctx_create(self.dev_index, self.chunk_frames, C.byref(self._ctx)))
-        self._ws = None
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev_index).cuda_stream)
+        self._create(self.dev_index, self.chunk_frames)
 
     def load(self, sd, prefix="cnn.resnet."):
         keep = []
@@ -349,15 +317,6 @@ class FlowCNNEngine:
         with torch.cuda.device(self.dev_index):
             _lib.check_flow(self.lib.egoego_flow_load_weights(self._ctx, C.byref(w), self._stream()))
         del keep
-
-    def _workspace(self, N):
-        n = self.lib.egoego_flow_workspace_bytes(self._ctx, N)
-        if n == 0:
-            raise _lib.EgoEgoHipError(self.lib.egoego_flow_last_error().decode())
-        if self._ws is None or self._ws.numel() < n + 256:
-            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-        off = (-self._ws.data_ptr()) % 256
-        return self._ws.data_ptr() + off, self._ws.numel() - off
 
     def features(self, flow, stages=False):
         """flow [N, 224, 224, 2] fp32 -> [N, 512] (+ the five stage activations, NHWC, when `stages`)."""
@@ -378,17 +337,6 @@ class FlowCNNEngine:
             st.append(dbg[o:o + N * h * w * c].view(N, h, w, c))
             o += N * h * w * c
         return out, st
-
-    def close(self):
-        if getattr(self, "_ctx", None) and self._ctx.value:
-            self.lib.egoego_flow_ctx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _BasicBlock(nn.Module):
@@ -424,7 +372,7 @@ class _ResNet(nn.Module):
         self.resnet = _ResNet18()
 
 
-class FlowFeatureExtractor(nn.Module):
+class FlowFeatureExtractor(EngineCacheMixin, nn.Module):
     """Drop-in for RN FeatureExtractor (lines 25-50) in eval mode: data['of'] [B, T, 224, 224, 2] -> [B, T, 512], on
     libegoego_hip (split-bf16 implicit-GEMM convolutions, BatchNorm with the running statistics).
 
@@ -434,6 +382,8 @@ class FlowFeatureExtractor(nn.Module):
     calibration pass.  The module starts in eval mode.  Training mode would
     normalise with batch statistics, which is not implemented: forward() and extract() raise in train().  `chunk_frames` bounds
     the frames per pass through the workspace (0 = the library's default, 256)."""
+
+    ENGINE = FlowCNNEngine
 
     def __init__(self, device=None, chunk_frames=0, seed=0, state_dict=None):
         super().__init__()
@@ -448,16 +398,6 @@ class FlowFeatureExtractor(nn.Module):
         self._engine = None
         self._packed = None
         self.eval()
-
-    def to(self, *args, **kwargs):
-        """RN:33-36: moves the parameters like nn.Module.to and remembers the device the features are computed on (any form
-        of the call: positional or keyword device, tensor, dtype only).  A CPU device makes extract() raise: there is no CPU
-        path."""
-        device = torch._C._nn._parse_to(*args, **kwargs)[0]
-        if device is not None:
-            self.device = torch.device(device)
-        super().to(*args, **kwargs)
-        return self
 
     def cuda(self, device=None):
         super().cuda(device)
@@ -475,19 +415,8 @@ class FlowFeatureExtractor(nn.Module):
     def _params_version(self):  # (not `_version`: nn.Module stores its state-dict format version under that name)
         return tuple((p.data_ptr(), p._version) for p in self.state_dict().values())
 
-    def engine(self):
-        dev = self.device
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        e = self._engine
-        if e is None or e.device != dev or e.chunk_frames != self.chunk_frames:
-            self._engine = FlowCNNEngine(dev, self.chunk_frames)
-            self._packed = None
-        v = self._params_version()
-        if v != self._packed:
-            self._engine.load(self.state_dict())
-            self._packed = v
-        return self._engine
+    def _engine_state(self):
+        return self.state_dict()
 
     def _check(self, flow):
         if self.training:
