@@ -23,6 +23,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name in ("evaluate_samples", "determine_floor_height_and_contacts", "compute_metrics_for_smpl"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("build_motion_windows", "window_table", "MotionWindows", "MotionWindowDataset", "rest_pose_offsets"):
+        from . import motion_data
+        return getattr(motion_data, name)
     if name == "HipEngine":
         from .engine import HipEngine
         return HipEngine

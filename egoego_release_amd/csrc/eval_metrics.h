@@ -3,8 +3,8 @@
 // (kinpoly/scripts/eval_metrics_imu_rec.py:66-107, 222-342 over kinpoly/relive/utils/metrics.py:15-24, 64-82), batched over
 // sequences of different lengths.  Joint layout: 22 SMPL joints, z up.
 //
-//   eval_fk_kernel       one fp64 thread per frame; quaternions (w >= 0) and joints rounded once to fp32.  (The prefix kernel's
-//                        Quat helpers in pointwise.h are fp32; the same formulas are restated here on doubles.)
+//   eval_fk_kernel       one fp64 thread per frame; quaternions (w >= 0) and joints rounded once to fp32 (the fp64
+//                        quaternion helpers: quat_f64.h).
 //   eval_floor_kernel    one 1024-thread workgroup per sequence; everything between the joint read and the results lives in LDS.
 //   eval_metrics_kernel  one 256-thread workgroup per (sample, ground truth) pair; fp64 accumulators, thread t owns frames
 //                        t, t + 256, ... and the partial sums meet in a fixed shuffle / LDS order, so a sample's numbers depend
@@ -32,6 +32,7 @@
 //   7. contacts from the velocity flags and the heights above floor_height (not the offset height).
 #pragma once
 #include "common.h"
+#include "quat_f64.h"
 
 namespace evalm {
 
@@ -54,36 +55,6 @@ static constexpr float TERRAIN_H = 0.04f, ROOT_H = 0.04f, FLOOR_OFFSET = 0.01f;
 EG_HD constexpr int contact_joint(int k) { return k == 0 ? 10 : k == 1 ? 11 : k == 2 ? 7 : k == 3 ? 8 : k == 4 ? 20 : k == 5 ? 21 : k == 6 ? 4 : 5; }
 
 // ---------------------------------------------------------------- forward kinematics
-struct QuatD {
-    double w, x, y, z;
-};
-EG_D QuatD qd_mul(QuatD a, QuatD b) {
-    return QuatD{a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-                 a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-}
-EG_D QuatD qd_std(QuatD q) { return q.w < 0.0 ? QuatD{-q.w, -q.x, -q.y, -q.z} : q; }
-// (cos(a / 2), sin(a / 2) / a * v), the factors from their series below 1e-6
-EG_D QuatD qd_from_aa(double x, double y, double z) {
-    const double a2 = x * x + y * y + z * z;
-    double s, c;
-    if (a2 < 1e-12) {
-        s = 0.5 - a2 / 48.0;
-        c = 1.0 - a2 / 8.0;
-    } else {
-        const double a = sqrt(a2);
-        s = sin(0.5 * a) / a;
-        c = cos(0.5 * a);
-    }
-    return qd_std(QuatD{c, x * s, y * s, z * s});
-}
-// p + w t + q.xyz x t with t = 2 q.xyz x p (unit q)
-EG_D void qd_rotate(QuatD q, const double (&p)[3], double (&o)[3]) {
-    const double tx = 2.0 * (q.y * p[2] - q.z * p[1]), ty = 2.0 * (q.z * p[0] - q.x * p[2]), tz = 2.0 * (q.x * p[1] - q.y * p[0]);
-    o[0] = p[0] + q.w * tx + (q.y * tz - q.z * ty);
-    o[1] = p[1] + q.w * ty + (q.z * tx - q.x * tz);
-    o[2] = p[2] + q.w * tz + (q.x * ty - q.y * tx);
-}
-
 struct FkArgs {
     const float* root;  // [N][3]
     const float* aa;    // [N][22][3] local axis-angle

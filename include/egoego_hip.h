@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*) and the evaluation (egoego_eval_*) were added under 8: purely additive, no existing entry changed */
+#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*) and the motion windows (egoego_win_*) were added under 8: purely additive, no existing entry changed */
 
 enum {
     EGOEGO_OK = 0,
@@ -461,6 +461,37 @@ int egoego_eval_root_to_floor(const float* d_jpos, const float* d_floor_height, 
 /* d_best [n_groups] int32: per group g the first b with d_group[b] == g (NULL = all 0) whose d_metrics[b][column] is smallest,
  * -1 for an empty group. */
 int egoego_eval_best(const double* d_metrics, int column, const int32_t* d_group, int B, int n_groups, int32_t* d_best, void* stream);
+
+/* ==================================================================================================================
+ * Stage-2 motion windows (egoego_win_*; added under ABI 8, purely additive): raw SMPL-H motion -> what the reference's
+ * AMASSDataset stores per window (egoego/data/amass_diffusion_dataset.py:409-510), its min / max statistics (355-377) and the
+ * normalised model input of __getitem__ (515-538).  Every tensor is a device tensor unless it says host.  The frames of all
+ * sequences are concatenated ([F] rows); window n covers the d_length[n] (0..W) frames from row d_first[n] and is padded with
+ * zero rows to W.  A window whose rows would leave the [F] frames is written as an empty one.  The entries keep no state.  A
+ * window's rows depend on its own frames only: they are bit-identical alone, anywhere in a batch and under any W that holds them.
+ * egoego_win_last_error() describes the last failure of an egoego_win_* call.
+ * ================================================================================================================== */
+const char* egoego_win_last_error(void);
+/* The largest window W the entries accept: a window's positions stay in LDS. */
+int egoego_win_max_window(void);
+/* d_trans [F][3], d_root_orient [F][3], d_body_pose [F][63], d_rest_offsets [22][3]; parents_host: 22 ints on the host,
+ * parents[j] < j for j >= 1.  Per window: d_jpos [N][W][66] (joints after FK, turned by the inverse of the first frame's head
+ * heading when `canonicalize` is set, shifted so that this head's xy is 0), d_jvel [N][W][66] (jpos[t + 1] - jpos[t] on the fp32
+ * values; zero in the last real frame), d_grot6d / d_lrot6d [N][W][132] (the first two rows of the global / local rotation
+ * matrices), d_recover [N][4] (the heading quaternion w, x, y, z; the identity without `canonicalize`).  fp64 inside, each output
+ * rounded once.  One workgroup per window. */
+int egoego_win_build(const float* d_trans, const float* d_root_orient, const float* d_body_pose, int n_frames, const float* d_rest_offsets,
+                     const int32_t* parents_host, const int32_t* d_first, const int32_t* d_length, int N, int W, int canonicalize,
+                     float* d_jpos, float* d_jvel, float* d_grot6d, float* d_lrot6d, float* d_recover, void* stream);
+/* d_stats [4][66]: min jpos, max jpos, min jvel, max jvel per coordinate over the real frames of all N windows (the zero
+ * velocity of each window's last frame included), exactly.  The workspace (256-byte aligned) holds the per-workgroup partials. */
+size_t egoego_win_stats_workspace_bytes(int N, int W);
+int egoego_win_stats(const float* d_jpos, const float* d_jvel, const int32_t* d_length, int N, int W, float* d_stats, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* d_motion [N][W][198]: (jpos - min) / (max - min) * 2 - 1 in fp32 (d_jpos_min / d_jpos_max [66]; a coordinate with max == min
+ * divides by zero, as in the reference), then d_grot6d; zero rows past each length. */
+int egoego_win_motion(const float* d_jpos, const float* d_grot6d, const int32_t* d_length, const float* d_jpos_min, const float* d_jpos_max,
+                      int N, int W, float* d_motion, void* stream);
 
 #ifdef __cplusplus
 }

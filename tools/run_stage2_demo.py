@@ -15,9 +15,10 @@ of this repo: every asset is an input file, and without `--w
   --head_pose     .npy [T,7] or [B,T,7]: xyz + quaternion (w,x,y,z), what trainer.full_body_gen_cond_head_pose_sliding_window
                   takes (trainer_amass_cond_motion_diffusion.py:261-276); or the reference's demo pickle
                   (test_data/ares/demo_ares_data.p: its 'head_qpos')
-  --stats         the dataset's min/max statistics pickle (global_jpos_min / global_jpos_max, amass_diffusion_dataset.py:232-239)
-  --rest_offsets  .npy [22,3] rest-pose joint offsets (AMASSDataset.rest_human_offsets; needs the licensed SMPL-H model to
-                  produce); --parents optionally overrides the SMPL-H kintree
+  --stats         the dataset's min/max statistics pickle (global_jpos_min / global_jpos_max, amass_diffusion_dataset.py:232-239;
+                  tools/build_motion_windows.py writes it from the raw motion)
+  --rest_offsets  .npy [22,3] rest-pose joint offsets (AMASSDataset.rest_human_offsets; tools/build_motion_windows.py writes it
+                  from the licensed SMPL-H model); --parents optionally overrides the SMPL-H kintree
   --gt_jpos       optional .npy [T,22,3] ground-truth global joints -> MPJPE (mm) and, under "metrics", the position keys of
                   compute_metrics_for_smpl per sample (egoego_release_amd.evaluate, on the device; the foot sliding of the samples
                   is measured from each sample's own floor height, the ground truth's from 0)
