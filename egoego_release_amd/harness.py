@@ -222,6 +222,41 @@ def _window_prefix_hip(ds, aa, root, n_last, parents=None):
     return out
 
 
+def _window_condition_torch(ds, jpos, quat):
+    """The torch chain of M:355-378 that _window_condition_hip stands in for: rotate_at_frame about the first frame, its xy moved to
+    the origin, head position and 6D rotation written into an otherwise zero x_start, joint positions normalised by `ds`.
+    jpos [B,Tw,3], quat [B,Tw,4] -> (x_start [B,Tw,198], recover [B,1,1,4])."""
+    b = jpos.shape[0]
+    al_trans, al_quat, recover = rotate_at_frame(jpos, quat, 0)
+    move0 = al_trans[:, 0:1, :].clone()
+    move0[:, :, 2] = 0
+    al_trans = al_trans - move0
+    al_6d = R.matrix_to_rotation_6d(R.quaternion_to_matrix(al_quat))
+    x_start = torch.zeros(b, al_6d.shape[1], 198, device=jpos.device)
+    x_start[:, :, HEAD_IDX * 3:HEAD_IDX * 3 + 3] = al_trans.float()
+    x_start[:, :, 66 + HEAD_IDX * 6:66 + HEAD_IDX * 6 + 6] = al_6d.float()
+    x_start[:, :, :66] = ds.normalize_jpos_min_max(x_start[:, :, :66].reshape(-1, 22, 3)).reshape(b, -1, 66)
+    return x_start, recover
+
+
+def _window_prefix_torch(ds, aa, root, n_last, parents):
+    """The torch chain of M:399-467 that _window_prefix_hip stands in for: ds.fk_smpl (which carries its own tree; `parents` is
+    what the HIP form is given) of the window, its last `n_last` frames re-canonicalised about their first frame's head heading,
+    normalised, rotations as 6D.  aa [B,Tw,22,3], root [B,Tw,3] -> [B,n_last,198]."""
+    b = aa.shape[0]
+    gq, gj = ds.fk_smpl(root.reshape(-1, 3), aa.reshape(-1, 22, 3))
+    gq = gq.reshape(b, -1, 22, 4)[:, -n_last:]
+    gj = gj.reshape(b, -1, 22, 3)[:, -n_last:]
+    t_trans, _, t_rec = rotate_at_frame(gj[:, :, HEAD_IDX, :], gq[:, :, HEAD_IDX, :], 0)
+    t_move = t_trans[:, 0:1, :].clone()
+    t_move[:, :, 2] = 0
+    inv = R.quaternion_invert(t_rec.float()).expand(b, gj.shape[1], 22, 4)
+    pj = R.quaternion_apply(inv, gj) - t_move[:, :, None, :]
+    pj = ds.normalize_jpos_min_max(pj.reshape(-1, 22, 3)).reshape(b, -1, 66)
+    p6 = R.matrix_to_rotation_6d(R.quaternion_to_matrix(R.quaternion_multiply(inv, gq))).reshape(b, -1, 132)
+    return torch.cat((pj, p6), dim=-1).float().contiguous()
+
+
 def window_spans(num_frames, seq_len):
     """(first frame, length) of every window the sliding-window loop runs over a `num_frames` trajectory (M:350-356): stride
     seq_len - 10, a trailing window of at most 10 frames is dropped."""
@@ -289,15 +324,7 @@ def p_sample_loop_sliding_window_w_canonical(model, ds, shape, global_head_jpos,
         if cond is not None:
             x_start, recover = cond
         else:
-            al_trans, al_quat, recover = rotate_at_frame(cur_jpos, cur_quat, 0)
-            move0 = al_trans[:, 0:1, :].clone()
-            move0[:, :, 2] = 0
-            al_trans = al_trans - move0
-            al_6d = R.matrix_to_rotation_6d(R.quaternion_to_matrix(al_quat))
-            x_start = torch.zeros(b, al_6d.shape[1], 198, device=device)
-            x_start[:, :, HEAD_IDX * 3:HEAD_IDX * 3 + 3] = al_trans.float()
-            x_start[:, :, 66 + HEAD_IDX * 6:66 + HEAD_IDX * 6 + 6] = al_6d.float()
-            x_start[:, :, :66] = ds.normalize_jpos_min_max(x_start[:, :, :66].reshape(-1, 22, 3)).reshape(b, -1, 66)
+            x_start, recover = _window_condition_torch(ds, cur_jpos, cur_quat)
         cm = cond_mask[:, t_idx:t_idx + seq_len].to(device)
         cn = noise["cond"][w_idx].to(device) if noise is not None else torch.randn_like(x_start)
         x_cond = (x_start * (1.0 - cm) + cm * cn).float().contiguous()
@@ -330,17 +357,7 @@ def p_sample_loop_sliding_window_w_canonical(model, ds, shape, global_head_jpos,
             prefix = hip_prefix
             w_idx += 1
             continue
-        gq, gj = ds.fk_smpl(root.reshape(-1, 3), aa.reshape(-1, 22, 3))
-        gq = gq.reshape(b, -1, 22, 4)[:, -seq_len + stride:]
-        gj = gj.reshape(b, -1, 22, 3)[:, -seq_len + stride:]
-        t_trans, _, t_rec = rotate_at_frame(gj[:, :, HEAD_IDX, :], gq[:, :, HEAD_IDX, :], 0)
-        t_move = t_trans[:, 0:1, :].clone()
-        t_move[:, :, 2] = 0
-        inv = R.quaternion_invert(t_rec.float()).expand(b, gj.shape[1], 22, 4)
-        pj = R.quaternion_apply(inv, gj) - t_move[:, :, None, :]
-        pj = ds.normalize_jpos_min_max(pj.reshape(-1, 22, 3)).reshape(b, -1, 66)
-        p6 = R.matrix_to_rotation_6d(R.quaternion_to_matrix(R.quaternion_multiply(inv, gq))).reshape(b, -1, 132)
-        prefix = torch.cat((pj, p6), dim=-1).float().contiguous()
+        prefix = _window_prefix_torch(ds, aa, root, seq_len - stride, parents)
         w_idx += 1
     return whole_aa, whole_root
 

@@ -108,27 +108,31 @@ class SkeletonOracle:
     def denorm(self, j):
         return (j + 1) * 0.5 * (self.hi - self.lo) + self.lo
 
-    def fk(self, root, aa):
+    def fk(self, root, aa, parents=None):
+        parents = PARENTS if parents is None else parents
         n = aa.shape[0]
         lq = mat_to_quat(Rot.from_rotvec(aa.reshape(-1, 3)).as_matrix().reshape(n, 22, 3, 3))
         gp, gr = [np.repeat(self.off[None, :1], n, 0)], [lq[:, :1]]
         for i in range(1, 22):
-            p = PARENTS[i]
+            p = parents[i]
             gp.append(quat_mul_vec(gr[p], np.repeat(self.off[None, i:i + 1], n, 0)) + gp[p])
             gr.append(std_mul(gr[p], lq[:, i:i + 1]))
         return np.concatenate(gr, 1), np.concatenate(gp, 1) + root[:, None, :]
 
 
-def convert_model_res_to_data(ds, x, recover):
-    """M:469-525.  x [B,T,198] float array, recover [B,1,1,4]."""
+def convert_model_res_to_data(ds, x, recover, parents=None, head=None):
+    """M:469-525.  x [B,T,198] float array, recover [B,1,1,4].  parents / head: another kinematic tree and head joint than the
+    reference's (the C ABI takes both as inputs)."""
+    parents = PARENTS if parents is None else parents
+    head = HEAD if head is None else head
     bs = x.shape[0]
     jpos = ds.denorm(x[:, :, :66].reshape(-1, 22, 3)).reshape(bs, -1, 22, 3)
     n = jpos.shape[1]
     gq = mat_to_quat(rot6d_to_mat(x[:, :, 66:].reshape(bs, n, 22, 6)))
     oq = std_mul(np.broadcast_to(recover, gq.shape), gq)
     rec = np.broadcast_to(recover.reshape(bs, 1, 4), (bs, n, 4))
-    root, head = quat_mul_vec(rec, jpos[:, :, 0]), quat_mul_vec(rec, jpos[:, :, HEAD])
-    par = list(PARENTS[1:])
+    root, head = quat_mul_vec(rec, jpos[:, :, 0]), quat_mul_vec(rec, jpos[:, :, head])
+    par = list(parents[1:])
     lq = np.concatenate([oq[..., :1, :], std_mul(quat_inv(oq[..., par, :]), oq[..., 1:, :])], -2)
     aa = Rot.from_quat(_to_scipy(lq).reshape(-1, 4)).as_rotvec().reshape(bs, n, 22, 3)
     return aa, root, head
