@@ -40,6 +40,10 @@ struct AttnArgs {
     int H;
     int L;     // valid keys (T + 1); keys >= L are padding and get probability 0
     int bh0;   // first (batch, head) pair of this launch (window-chunked launches)
+    // ragged calls (the RAG instantiations only): per-window frame counts, window b has lens[b] + 1 valid keys (common.h window_keys);
+    // a key tile wholly beyond them comes out as probability 0 like any other masked key
+    const int32_t* lens;
+    const StepState* state;
 };
 
 // QREG: the Q fragments are not read from global memory but handed over in registers by the caller
@@ -53,7 +57,7 @@ __device__ __forceinline__ void static_phases(F& f) {
     }
 }
 
-template <int KT, int NP, bool QREG = false, int CH = 4>
+template <int KT, int NP, bool QREG = false, int CH = 4, bool RAG = false>
 __device__ __forceinline__ void attn_body(const AttnArgs& a, int bh, int qblock, char* smem,
                                           const bf16x8* qreg_h = nullptr, const bf16x8* qreg_l = nullptr) {
     static_assert((CH == 4 || CH == 2) && (KT * NP * CH) % 4 == 0, "chunk width");
@@ -68,6 +72,8 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bh, int qblock,
     const int qt_raw = qblock * 4 + wave;
     const bool active = qt_raw < KT;
     const int qt = active ? qt_raw : KT - 1;
+    int L = a.L;
+    if constexpr (RAG) L = window_keys(a.lens, a.state, bh / a.H, a.L);
 
     auto stage_src = [&](int ph, int j) -> const u32x4* {
         const int blk = j * 4 + wave;
@@ -180,7 +186,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bh, int qblock,
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = 32 * kt + mfma32_row(r, hf);
-                    if (key >= a.L) s[kt][r] = -INFINITY;
+                    if (key >= L) s[kt][r] = -INFINITY;
                     mx = fmaxf(mx, s[kt][r]);
                 }
             mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -271,7 +277,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bh, int qblock,
 template <int KT, int NP> constexpr int attn_chunk() { return (KT <= 4 || EGOEGO_ATTN_CH4 || (KT * NP * 2) % 4 != 0) ? 4 : 2; }
 template <int KT, int NP> constexpr int attn_smem() { return 2 * KT * NP * attn_chunk<KT, NP>() * 1024; }
 
-template <int KT, int NP>
+template <int KT, int NP, bool RAG = false>
 __global__ __launch_bounds__(256, (attn_smem<KT, NP>() <= 80 * 1024 && !(EGOEGO_ATTN_CH4 && KT > 4) ? 2 : 1)) void attn_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifndef EGOEGO_ATTN_NOREMAP
@@ -281,7 +287,7 @@ __global__ __launch_bounds__(256, (attn_smem<KT, NP>() <= 80 * 1024 && !(EGOEGO_
     // the second read of a chunk comes out of that XCD's L2
     const int nqb = (int)gridDim.x;
     const int lid = EGOEGO_ATTN_NOREMAP ? (int)(blockIdx.y * nqb + blockIdx.x) : xcd_remap((int)(blockIdx.y * nqb + blockIdx.x), nqb * (int)gridDim.y);
-    attn_body<KT, NP, false, attn_chunk<KT, NP>()>(a, lid / nqb + a.bh0, lid % nqb, smem);
+    attn_body<KT, NP, false, attn_chunk<KT, NP>(), RAG>(a, lid / nqb + a.bh0, lid % nqb, smem);
 }
 
 // ---- The long window (KT = 7 key tiles, <= 224 tokens) on EIGHT waves: one workgroup per (window, head) ------------------------------
@@ -303,7 +309,7 @@ EG_D u32x4 load16_untracked(const u32x4* p) {
     return v;
 }
 
-template <int KT, int NP>
+template <int KT, int NP, bool RAG = false>
 __global__ __launch_bounds__(512, 1) void attn8_kernel(AttnArgs a) {
     static_assert(NP == 2 && KT >= 5 && KT <= 8, "the split-bf16 long window");
     constexpr int CH = 2, NKP = 16 / CH, NPH = 2 * NKP, NSLOT = 4;
@@ -319,6 +325,8 @@ __global__ __launch_bounds__(512, 1) void attn8_kernel(AttnArgs a) {
     const int lane = threadIdx.x & 63, hf = lane >> 5, col = lane & 31;
     const bool active = wave < KT;
     const int qt = active ? wave : KT - 1;
+    int L = a.L;
+    if constexpr (RAG) L = window_keys(a.lens, a.state, bh / a.H, a.L);
 
     auto stage_src = [&](int ph, int j) -> const u32x4* {
         const int blk = min(j * 8 + wave, NBLK - 1);
@@ -441,7 +449,7 @@ __global__ __launch_bounds__(512, 1) void attn8_kernel(AttnArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int key = 32 * kt + mfma32_row(r, hf);
-                        if (key >= a.L) s[kt][r] = -INFINITY;
+                        if (key >= L) s[kt][r] = -INFINITY;
                         mx = fmaxf(mx, s[kt][r]);
                     }
                 mx = fmaxf(mx, __shfl_xor(mx, 32));

@@ -232,6 +232,10 @@ struct AttnCore8Args {
     size_t o8_plane;
     float* o_scale;
     int BH;     // (window, head) pairs of the launch; the grid is min(BH * ceil(KT / 4), compute units) persistent workgroups
+    // ragged calls (the RAG instantiations only): per-window frame counts, window b has lens[b] + 1 valid keys (common.h window_keys);
+    // the persistent workgroups load the count per item.  V's scales are per KEY here, so a masked key touches nothing but itself.
+    const int32_t* lens;
+    const StepState* state;
     EG_DBG(unsigned long long* trace;)  // perf-debug build: [item][8] phase timestamps or nullptr
 };
 
@@ -245,7 +249,7 @@ struct AttnCore8Args {
 // the CU to cover a wait) showed 5.7 of a workgroup's 26 us waiting for the first 120 KB (K half + Q: the whole chip starts a
 // round at once and gets ~11 B/clk per CU) and the second K half arriving behind the first half's MFMAs.  Every wait is a full
 // vmcnt(0): what is waited for was requested a phase earlier.  Items are computed exactly as before: same bits.
-template <int KT, bool O8>
+template <int KT, bool O8, bool RAG = false>
 __global__ __launch_bounds__(256, 1) void attn_core_i8_kernel(AttnCore8Args a) {
     constexpr int HALF = KT * 4 * 1024;  // bytes of one slice of half an image (4 of the 8 d blocks x KT tiles)
     constexpr int BUF = 2 * HALF;        // one buffer: both slices of a half image
@@ -272,11 +276,14 @@ __global__ __launch_bounds__(256, 1) void attn_core_i8_kernel(AttnCore8Args a) {
     // ---- what an item needs before its first MFMA
     struct Front {
         int bh, qt, tile_active;
+        int L;  // valid keys of the item's window
         float sq, skr, svr;
         int touch, touch2;
     };
     auto locate = [&](int it, Front& f) {
         f.bh = it / NQB;
+        f.L = a.L;
+        if constexpr (RAG) f.L = window_keys(a.lens, a.state, f.bh / a.H, a.L);
         const int qt_raw = (it - f.bh * NQB) * 4 + wave;
         f.tile_active = qt_raw < KT;
         f.qt = f.tile_active ? qt_raw : KT - 1;
@@ -340,6 +347,7 @@ __global__ __launch_bounds__(256, 1) void attn_core_i8_kernel(AttnCore8Args a) {
         const int next = item + (int)gridDim.x;
         const bool has_next = next < n_items;  // workgroup-uniform
         const int bh = cur.bh, qt = cur.qt;
+        const int Lb = RAG ? cur.L : a.L;
         const int b = bh / a.H, h = bh - b * a.H;
         const bool active = cur.tile_active && qt * 32 + col < a.Lr;  // per lane: the last query tile may reach beyond the window's rows
         const float sq = cur.sq;
@@ -440,7 +448,7 @@ __global__ __launch_bounds__(256, 1) void attn_core_i8_kernel(AttnCore8Args a) {
                     for (int c = 0; c < 4; ++c) {
                         const int r = 4 * gq + c;
                         float val = (float)i8_combine(s[kt].h[r], s[kt].m[r]) * (sq256 * ks[c]);
-                        if (kt * 32 + 8 * gq + 4 * hf + c >= a.L) val = -INFINITY;
+                        if (kt * 32 + 8 * gq + 4 * hf + c >= Lb) val = -INFINITY;
                         p[kt][r] = val;
                         mx = fmaxf(mx, val);
                     }

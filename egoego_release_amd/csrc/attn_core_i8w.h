@@ -24,7 +24,7 @@
 template <int KT>
 static constexpr int attn_core8w_smem_bytes() { return 2 * KT * 4 * 1024 + 3 * 4 * KT * 1024; }  // K/V buffer 0 + the P image (over buffer 1 and beyond)
 
-template <int KT, bool O8>
+template <int KT, bool O8, bool RAG = false>
 __global__ __launch_bounds__(512, 2) void attn_core_i8w_kernel(AttnCore8Args a) {
     static_assert(KT > 4 && KT <= 8, "the pair splits the key tiles 4 + (KT - 4)");
     constexpr int HALF = KT * 4 * 1024;  // bytes of one slice of half an image (4 of the 8 d blocks x KT tiles)
@@ -50,11 +50,14 @@ __global__ __launch_bounds__(512, 2) void attn_core_i8w_kernel(AttnCore8Args a) 
 
     struct Front {
         int bh, qt, tile_active;
+        int L;  // valid keys of the item's window
         float sq, skr, svr;
         int touch, touch2;
     };
     auto locate = [&](int it, Front& f) {
         f.bh = it / NQB;
+        f.L = a.L;
+        if constexpr (RAG) f.L = window_keys(a.lens, a.state, f.bh / a.H, a.L);
         const int qt_raw = (it - f.bh * NQB) * 4 + qt3;
         f.tile_active = qt_raw < KT;
         f.qt = f.tile_active ? qt_raw : KT - 1;
@@ -121,6 +124,7 @@ __global__ __launch_bounds__(512, 2) void attn_core_i8w_kernel(AttnCore8Args a) 
         const int next = item + (int)gridDim.x;
         const bool has_next = next < n_items;  // workgroup-uniform
         const int bh = cur.bh, qt = cur.qt;
+        const int Lb = RAG ? cur.L : a.L;  // (the next item's count is located before this item's softmax)
         const int b = bh / a.H, h = bh - b * a.H;
         const bool active = cur.tile_active && qt * 32 + col < a.Lr;
         const float sq = cur.sq;
@@ -211,7 +215,7 @@ __global__ __launch_bounds__(512, 2) void attn_core_i8w_kernel(AttnCore8Args a) 
                     for (int c = 0; c < 4; ++c) {
                         const int r = 4 * gq + c;
                         float val = (float)i8_combine(s[kt].h[r], s[kt].m[r]) * (sq256 * ks[c]);
-                        if (MASKED && (T0 + kt) * 32 + 8 * gq + 4 * hf + c >= a.L) val = -INFINITY;
+                        if (MASKED && (T0 + kt) * 32 + 8 * gq + 4 * hf + c >= Lb) val = -INFINITY;
                         p[kt][r] = val;
                         mx = fmaxf(mx, val);
                     }
@@ -219,7 +223,7 @@ __global__ __launch_bounds__(512, 2) void attn_core_i8w_kernel(AttnCore8Args a) 
             };
 #pragma unroll
             for (int kt = 0; kt < NT; ++kt) {
-                if ((T0 + kt) * 32 + 32 <= a.L) logits(kt, std::false_type{});
+                if ((T0 + kt) * 32 + 32 <= Lb) logits(kt, std::false_type{});  // (ragged: any tile may be the masked one, or lie wholly beyond the keys)
                 else logits(kt, std::true_type{});
             }
             mx = fmaxf(mx, __shfl_xor(mx, 32));

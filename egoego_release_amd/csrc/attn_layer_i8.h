@@ -39,7 +39,20 @@ struct AttnLayerArgs {
     int8_t* o8;
     size_t o8_plane;
     float* o_scale;
+    // ragged calls (the RAG instantiations only): per-window frame counts, window b has lens[b] + 1 valid keys (common.h window_keys)
+    const int32_t* lens;
+    const StepState* state;
 };
+
+// V's scales are per feature COLUMN over the window's keys, so in a ragged window the rows of the keys [Lb, L) — whatever the
+// frames past the window's length held — must not take part: they become 0 before the column maximum is taken (they meet
+// probability 0 either way).  The rows from L on, which pad every window alike, stay as they are: with Lb == L nothing changes and
+// the bits are those of a uniform call.  key: the row of accumulator register r (un-swapped accumulator: registers walk the keys).
+template <bool RAG>
+EG_D float v_ragged(float v, int key, int Lb, int L) {
+    if constexpr (RAG) return (key >= Lb && key < L) ? 0.f : v;
+    return v;
+}
 
 using AL8K = GemmCfg<4, 2, 2, 2, 1, 2, false, 1, 3>;
 using AL8V = GemmCfg<4, 2, 2, 2, 1, 2, true, 1, 3>;

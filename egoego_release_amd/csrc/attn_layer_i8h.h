@@ -19,6 +19,7 @@
 using AH8Q = GemmCfg<2, 1, 4, 2, 1, 2, false, 2, 3>;  // 256 features x 64 queries; its 20 one-KiB blocks per stage go unevenly over 8 waves (gemm.h)
 static_assert(AH8Q::SMEM_BYTES <= AW8K::SMEM_BYTES, "the Q half fits the ring of the K / V projections");
 
+template <bool RAG = false>
 __global__ __launch_bounds__(512, 2) void attn_layer_i8h_kernel(AttnLayerArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* kv = smem;                               // K image, later V^T image: [slice][tile][k32 block][1 KiB]
@@ -34,6 +35,8 @@ __global__ __launch_bounds__(512, 2) void attn_layer_i8h_kernel(AttnLayerArgs a)
     const int lid = xcd_remap((int)blockIdx.x, (int)gridDim.x);  // both halves and all H heads of a window share an XCD
     const int bh = (lid >> 1) + a.bh0, qh = lid & 1;
     const int b = bh / a.H, h = bh - b * a.H;
+    int Lb = a.L;  // this window's valid keys
+    if constexpr (RAG) Lb = window_keys(a.lens, a.state, b, a.L);
     const int wave = wave_id_uniform();
     const int lane = threadIdx.x & 63, hf = lane >> 5, col = lane & 31;
     const int wf = wave & 3, wt = wave >> 2;       // projections: feature quarter, token half (K, V) / query tile (Q)
@@ -174,7 +177,7 @@ __global__ __launch_bounds__(512, 2) void attn_layer_i8h_kernel(AttnLayerArgs a)
             for (int c = 0; c < 4; ++c) {
                 const int r = 4 * gq + c;
                 float val = (float)i8_combine(s.h[r], s.m[r]) * (sq256 * ks[c]);
-                if (kt * 32 + 8 * gq + 4 * hf + c >= a.L) val = -INFINITY;
+                if (kt * 32 + 8 * gq + 4 * hf + c >= Lb) val = -INFINITY;
                 p[r] = val;
                 mx = fmaxf(mx, val);
             }
@@ -223,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void attn_layer_i8h_kernel(AttnLayerArgs a)
                 i8_dequant_rows(q[i][j], v[i][j], sw, p_hs + t0 + j * 32 + 4 * hf);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    v[i][j][r] += bf;
+                    v[i][j][r] = v_ragged<RAG>(v[i][j][r] + bf, t0 + j * 32 + mfma32_row(r, hf), Lb, a.L);
                     amax[i] = fmaxf(amax[i], fabsf(v[i][j][r]));
                 }
             }

@@ -32,6 +32,7 @@ static_assert(AW8K::SMEM_BYTES == AL8K::SMEM_BYTES, "same ring as the 4-wave for
 #endif
 static constexpr int AW_DYN_SMEM_BYTES = EGOEGO_ATTN_PREFETCH ? (int)GemmCfg<2, 2, 4, 2, 1, 2, false, 2, 3>::SMEM_BYTES : AL_SMEM_BYTES;
 
+template <bool RAG = false>
 __global__ __launch_bounds__(512, 2) void attn_layer_i8w_kernel(AttnLayerArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #if EGOEGO_ATTN_PREFETCH
@@ -62,6 +63,8 @@ __global__ __launch_bounds__(512, 2) void attn_layer_i8w_kernel(AttnLayerArgs a)
     const int lid = xcd_remap((int)blockIdx.x, (int)gridDim.x);  // the H heads of a window share an XCD (and its L2)
     const int bh = lid + a.bh0;
     const int b = bh / a.H, h = bh - b * a.H;
+    int Lb = a.L;  // this window's valid keys
+    if constexpr (RAG) Lb = window_keys(a.lens, a.state, b, a.L);
     const int wave = wave_id_uniform();
     const int lane = threadIdx.x & 63, hf = lane >> 5, col = lane & 31;
     const int wf = wave & 3, wt = wave >> 2;       // projections: feature quarter (64 features), token half (64 tokens)
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(512, 2) void attn_layer_i8w_kernel(AttnLayerArgs a)
                 for (int c = 0; c < 4; ++c) {
                     const int r = 4 * gq + c;
                     float val = (float)i8_combine(s[kt].h[r], s[kt].m[r]) * (sq256 * ks[c]);
-                    if ((2 * kh + kt) * 32 + 8 * gq + 4 * hf + c >= a.L) val = -INFINITY;
+                    if ((2 * kh + kt) * 32 + 8 * gq + 4 * hf + c >= Lb) val = -INFINITY;
                     p[kt][r] = val;
                     mx = fmaxf(mx, val);
                 }
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(512, 2) void attn_layer_i8w_kernel(AttnLayerArgs a)
                 i8_dequant_rows(q[i][j], v[i][j], sw, p_hs + t0 + j * 32 + 4 * hf);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    v[i][j][r] += bf;
+                    v[i][j][r] = v_ragged<RAG>(v[i][j][r] + bf, t0 + j * 32 + mfma32_row(r, hf), Lb, a.L);
                     amax[i] = fmaxf(amax[i], fabsf(v[i][j][r]));
                 }
             }

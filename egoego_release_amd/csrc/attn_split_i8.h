@@ -21,6 +21,7 @@ struct AttnSplitBufs {
     float* sv;     // [B*H][256] V column scales
 };
 
+template <bool RAG = false>
 __global__ __launch_bounds__(512, 2) void attn_proj_i8_kernel(AttnLayerArgs a, AttnSplitBufs o) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* red = (float*)smem;                     // [512] cross-wave maxima
@@ -32,6 +33,8 @@ __global__ __launch_bounds__(512, 2) void attn_proj_i8_kernel(AttnLayerArgs a, A
     const int bhl = lid / 3, which = lid - bhl * 3;              // 0 = Q, 1 = K, 2 = V
     const int bh = bhl + a.bh0;
     const int b = bh / a.H, h = bh - b * a.H;
+    int Lb = a.L;  // this window's valid keys
+    if constexpr (RAG) Lb = window_keys(a.lens, a.state, b, a.L);
     const int wave = wave_id_uniform();
     const int lane = threadIdx.x & 63, hf = lane >> 5, col = lane & 31;
     const int wf = wave & 3, wt = wave >> 2;
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(512, 2) void attn_proj_i8_kernel(AttnLayerArgs a, A
                 i8_dequant_rows(q[i][j], v[i][j], sw, p_hs + t0 + j * 32 + 4 * hf);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    v[i][j][r] += bf;
+                    v[i][j][r] = v_ragged<RAG>(v[i][j][r] + bf, t0 + j * 32 + mfma32_row(r, hf), Lb, a.L);
                     amax[i] = fmaxf(amax[i], fabsf(v[i][j][r]));
                 }
             }
@@ -151,6 +154,7 @@ using AP6K = GemmCfg<2, 2, 4, 1, 1, 2, false, 2, 3>;  // 256 features x 64 token
 using AP6V = GemmCfg<2, 2, 2, 2, 1, 2, true, 2, 3>;   // 128 features x 128 tokens (V half), un-swapped accumulator
 static constexpr int ATTN_PROJ6_SMEM = 8192 + (AP6K::SMEM_BYTES > AP6V::SMEM_BYTES ? AP6K::SMEM_BYTES : AP6V::SMEM_BYTES);
 
+template <bool RAG = false>
 __global__ __launch_bounds__(256, 2) void attn_proj6_i8_kernel(AttnLayerArgs a, AttnSplitBufs o) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* red = (float*)smem;                     // [256] cross-wave maxima
@@ -163,6 +167,8 @@ __global__ __launch_bounds__(256, 2) void attn_proj6_i8_kernel(AttnLayerArgs a, 
     const int which = part >> 1, half = part & 1;
     const int bh = bhl + a.bh0;
     const int b = bh / a.H, h = bh - b * a.H;
+    int Lb = a.L;  // this window's valid keys
+    if constexpr (RAG) Lb = window_keys(a.lens, a.state, b, a.L);
     const int wave = wave_id_uniform();
     const int lane = threadIdx.x & 63, hf = lane >> 5, col = lane & 31;
     const GemmOperands g{(const __bf16*)a.w8, a.w_plane / 2, (const __bf16*)a.h8, a.h_plane / 2, 16, 0, 0, 0 EG_DBG(, 0, nullptr)};
@@ -239,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void attn_proj6_i8_kernel(AttnLayerArgs a, 
                 i8_dequant_rows(q[i][j], v[i][j], sw, p_hs + t0 + j * 32 + 4 * hf);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    v[i][j][r] += bf;
+                    v[i][j][r] = v_ragged<RAG>(v[i][j][r] + bf, t0 + j * 32 + mfma32_row(r, hf), Lb, a.L);
                     amax[i] = fmaxf(amax[i], fabsf(v[i][j][r]));
                 }
             }
@@ -273,6 +279,7 @@ __global__ __launch_bounds__(256, 2) void attn_proj6_i8_kernel(AttnLayerArgs a, 
 // per GPU (the per-rank shard of the 8-GPU split of BASELINE configs[2]): 256 workgroups = ONE round of the chip, where the
 // three-workgroup form needs 1.5 rounds and the one-kernel form leaves half the CUs idle behind a 38-us serial chain.
 // Same configurations, same epilogue code per value, same images as the other split forms: same bits (round 4).
+template <bool RAG = false>
 __global__ __launch_bounds__(512, 2) void attn_proj2_i8_kernel(AttnLayerArgs a, AttnSplitBufs o) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* red = (float*)smem;                     // [512] cross-wave maxima
@@ -285,6 +292,8 @@ __global__ __launch_bounds__(512, 2) void attn_proj2_i8_kernel(AttnLayerArgs a, 
     const int which = 1 + part;                                  // the full projection of this part: 1 = K, 2 = V
     const int bh = bhl + a.bh0;
     const int b = bh / a.H, h = bh - b * a.H;
+    int Lb = a.L;  // this window's valid keys
+    if constexpr (RAG) Lb = window_keys(a.lens, a.state, b, a.L);
     const int wave = wave_id_uniform();
     const int lane = threadIdx.x & 63, hf = lane >> 5, col = lane & 31;
     const int wf = wave & 3, wt = wave >> 2;
@@ -361,7 +370,7 @@ __global__ __launch_bounds__(512, 2) void attn_proj2_i8_kernel(AttnLayerArgs a, 
                     i8_dequant_rows(q[i][j], v[i][j], sw, p_hs + t0 + j * 32 + 4 * hf);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        v[i][j][r] += bf;
+                        v[i][j][r] = v_ragged<RAG>(v[i][j][r] + bf, t0 + j * 32 + mfma32_row(r, hf), Lb, a.L);
                         amax[i] = fmaxf(amax[i], fabsf(v[i][j][r]));
                     }
                 }
@@ -437,6 +446,7 @@ __global__ __launch_bounds__(512, 2) void attn_proj2_i8_kernel(AttnLayerArgs a, 
     }
 }
 
+template <bool RAG = false>
 __global__ __launch_bounds__(512, 2) void attn_core_s_kernel(AttnLayerArgs a, AttnSplitBufs o) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* kv = smem;                               // K image, later V^T image
@@ -449,6 +459,8 @@ __global__ __launch_bounds__(512, 2) void attn_core_s_kernel(AttnLayerArgs a, At
     const int lid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int bh = lid + a.bh0;
     const int b = bh / a.H, h = bh - b * a.H;
+    int Lb = a.L;  // this window's valid keys
+    if constexpr (RAG) Lb = window_keys(a.lens, a.state, b, a.L);
     const int wave = wave_id_uniform();
     const int lane = threadIdx.x & 63, hf = lane >> 5, col = lane & 31;
     const int8_t* const img = o.img + (size_t)bh * 3 * 65536;
@@ -521,7 +533,7 @@ __global__ __launch_bounds__(512, 2) void attn_core_s_kernel(AttnLayerArgs a, At
                 for (int c = 0; c < 4; ++c) {
                     const int r = 4 * gq + c;
                     float val = (float)i8_combine(s[kt].h[r], s[kt].m[r]) * (sq256 * ks[c]);
-                    if ((2 * kh + kt) * 32 + 8 * gq + 4 * hf + c >= a.L) val = -INFINITY;
+                    if ((2 * kh + kt) * 32 + 8 * gq + 4 * hf + c >= Lb) val = -INFINITY;
                     p[kt][r] = val;
                     mx = fmaxf(mx, val);
                 }

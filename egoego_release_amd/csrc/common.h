@@ -227,14 +227,29 @@ struct StepState {
     const float* prefix;   // [B][prefix_len][D] in-painting source or nullptr
     uint64_t seed;         // Philox key
     int64_t window_offset; // global index of window 0 (shard-invariant noise)
+    // Ragged calls (egoego_sample_loop_ragged): per-window frame counts [B] (1..T) and per-window Philox ids [B], or nullptr
+    // (every window holds T frames / window b draws the stream of window_offset + b).  Like x, noise and prefix they are the
+    // caller's buffers of THIS call: the captured step reads them from here, never from a kernel argument.
+    const int32_t* lens;
+    const int64_t* window_ids;
     // Outlier monitor of the int8-slice precisions (egoego_outlier_stats): site 2 * layer + (0: LayerNorm-1, 1: LayerNorm-2) holds
     // the bit pattern of max |value| over every row that epilogue has quantised (one scale per row) since the last reset —
     // positive floats order like their bit patterns, so the kernels use one atomicMax per workgroup.  A site whose LayerNorm writes
     // no int8 rows in the running form stays 0 (which ones: include/egoego_hip.h).  Every row below B * Lr counts, each window's
     // padding rows included (zero under a row mask); the rows that pad the call to whole blocks do not.  Layers >= 8 are not recorded.
+    // A ragged call sets no row mask: the rows past a window's own length are computed like any others (they attend over the
+    // window's valid keys only, so they stay finite and inside the per-step clamp) and are recorded here as computed.
     unsigned ln_max[16];
 };
 static constexpr int OUTLIER_SITES = 16;
+
+// Valid keys of window b.  Uniform calls: L = T + 1 for every window (lens == nullptr and, in a loop, st->lens == nullptr).  Ragged
+// calls: lens[b] frames + the time token (key 0, always valid: a row maximum over the valid keys is finite).  In a multi-step loop
+// the array comes from the step state.  Wave-uniform: b is, and the value is moved to an SGPR.
+EG_D int window_keys(const int32_t* lens, const StepState* st, int b, int L) {
+    const int32_t* p = st ? st->lens : lens;
+    return p ? __builtin_amdgcn_readfirstlane(p[b]) + 1 : L;
+}
 
 // --------------------------------------------------------------------------------------------
 // Philox4x32-10 counter-based generator + Box-Muller: four N(0,1) per call.

@@ -66,10 +66,11 @@ struct LayerDev {
 // memory (Workspace::state, a StepState), so ONE graph serves every step of every chain of that shape on that workspace.
 struct StepKey {
     int B, T, mode, noise_mode, prefix_len, clip, ddim, has_mask;
+    int ragged;  // per-window lengths / ids: the step launches the ragged instantiations of the attention kernels and the posterior epilogue (the arrays are step state)
     const void* ws;
     bool operator==(const StepKey& o) const {
         return B == o.B && T == o.T && mode == o.mode && noise_mode == o.noise_mode && prefix_len == o.prefix_len && clip == o.clip &&
-               ddim == o.ddim && has_mask == o.has_mask && ws == o.ws;
+               ddim == o.ddim && has_mask == o.has_mask && ragged == o.ragged && ws == o.ws;
     }
 };
 struct StepGraph {
@@ -213,7 +214,7 @@ static void carve(const egoego_ctx* c, const Geometry& g, char* base, Workspace&
 // HBM, the attention launch disappears, and — since the two workgroups resident on a CU drift apart — one
 // workgroup's HBM/L2-bound attention phases overlap the other's MFMA-bound projections.
 // Valid when a window is exactly one token block of the QKV tile (Lp == 128).
-template <class CQK, class EQK, class CV, class EV, class CQ, int KT, int NP>
+template <class CQK, class EQK, class CV, class EV, class CQ, int KT, int NP, bool RAG = false>
 __global__ __launch_bounds__(CQK::NT, CQK::MINW) void qkv_attn_kernel(GemmOperands g, EQK eqk, EV ev, AttnArgs a, int H) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lid = xcd_remap((int)blockIdx.x, (int)gridDim.x);  // the H heads of a window share an XCD (and its L2)
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(CQK::NT, CQK::MINW) void qkv_attn_kernel(GemmOperan
     __syncthreads();
     EG_DBG(if (tr && threadIdx.x == 0) tr[3] = wall_clock64();
            if (g.ablate & 4) return;)
-    attn_body<KT, NP, true>(a, bh, 0, smem, qh, ql);
+    attn_body<KT, NP, true, 4, RAG>(a, bh, 0, smem, qh, ql);
     EG_DBG(if (tr) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (threadIdx.x == 0) tr[4] = wall_clock64();
@@ -440,9 +441,9 @@ static int launch_gemm(const GemmOperands& g, const Epi& epi, hipStream_t s) {
     return 0;
 }
 
-template <int KT, int NP>
+template <int KT, int NP, bool RAG>
 static int launch_attn_kt(const AttnArgs& a, int BH, hipStream_t s) {
-    auto kern = attn_kernel<KT, NP>;
+    auto kern = attn_kernel<KT, NP, RAG>;
     constexpr int smem = attn_smem<KT, NP>();
     static DevOnce once;
     if (once.pending()) {
@@ -459,9 +460,9 @@ static int launch_attn_kt(const AttnArgs& a, int BH, hipStream_t s) {
 #ifndef EGOEGO_ATTN_WG4
 #define EGOEGO_ATTN_WG4 0
 #endif
-template <int KT>
+template <int KT, bool RAG>
 static int launch_attn8_kt(const AttnArgs& a, int BH, hipStream_t s) {
-    auto kern = attn8_kernel<KT, 2>;
+    auto kern = attn8_kernel<KT, 2, RAG>;
     constexpr int smem = 4 * KT * 2 * 2 * 1024;
     static DevOnce once;
     if (once.pending()) {
@@ -473,18 +474,18 @@ static int launch_attn8_kt(const AttnArgs& a, int BH, hipStream_t s) {
     return 0;
 }
 
-template <int NP>
+template <int NP, bool RAG>
 static int launch_attn(const AttnArgs& a, int KT, int BH, hipStream_t s) {
     if constexpr (NP == 2) {
         // (same bits either way; below one workgroup per CU the two four-wave workgroups per (window, head) spread over twice the CUs:
         // B=1 0.447 against 0.453 ms per step)
-        if (KT == 7 && !EGOEGO_ATTN_WG4 && BH >= 256) return launch_attn8_kt<7>(a, BH, s);
+        if (KT == 7 && !EGOEGO_ATTN_WG4 && BH >= 256) return launch_attn8_kt<7, RAG>(a, BH, s);
     }
     switch (KT) {
-        case 1: return launch_attn_kt<1, NP>(a, BH, s);
-        case 2: return launch_attn_kt<2, NP>(a, BH, s);
-        case 4: return launch_attn_kt<4, NP>(a, BH, s);
-        case 7: return launch_attn_kt<7, NP>(a, BH, s);
+        case 1: return launch_attn_kt<1, NP, RAG>(a, BH, s);
+        case 2: return launch_attn_kt<2, NP, RAG>(a, BH, s);
+        case 4: return launch_attn_kt<4, NP, RAG>(a, BH, s);
+        case 7: return launch_attn_kt<7, NP, RAG>(a, BH, s);
     }
     return fail(EGOEGO_E_INVALID, "unsupported key-tile count %d", KT);
 }
@@ -617,26 +618,26 @@ static int launch_embed_tt(const EmbedArgs& ea, int rows, hipStream_t s) {
     HIP_TRY(hipGetLastError());
     return 0;
 }
-template <int TT, bool I8>
-static int launch_out_tt(const OutArgs& oa, int rows, hipStream_t s) {
+template <int TT, bool I8, bool IDS>
+static int launch_out_tt(const OutArgsT<IDS>& oa, int rows, hipStream_t s) {
     static DevOnce once;
     if (once.pending()) {
-        HIP_TRY(allow_smem((out_kernel<TT, 1, I8>), TT * 32 * 1024));
-        HIP_TRY(allow_smem((out_kernel<TT, 2, I8>), TT * 32 * 1024));
+        HIP_TRY(allow_smem((out_kernel<TT, 1, I8, IDS>), TT * 32 * 1024));
+        HIP_TRY(allow_smem((out_kernel<TT, 2, I8, IDS>), TT * 32 * 1024));
         once.done();
     }
     const int nb = rows / (32 * TT);
     if (nb <= 128)  // fewer token blocks than half the CUs: two workgroups per token block, 128 features each
-        out_kernel<TT, 2, I8><<<dim3(2 * nb), dim3(256), TT * 32 * 1024, s>>>(oa);
+        out_kernel<TT, 2, I8, IDS><<<dim3(2 * nb), dim3(256), TT * 32 * 1024, s>>>(oa);
     else
-        out_kernel<TT, 1, I8><<<dim3(nb), dim3(256), TT * 32 * 1024, s>>>(oa);
+        out_kernel<TT, 1, I8, IDS><<<dim3(nb), dim3(256), TT * 32 * 1024, s>>>(oa);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-template <int KT, bool O8>
+template <int KT, bool O8, bool RAG>
 static int launch_attn_core8_kt(AttnCore8Args a, int BH, hipStream_t s) {
-    auto kern = attn_core_i8_kernel<KT, O8>;
+    auto kern = attn_core_i8_kernel<KT, O8, RAG>;
     constexpr int smem = 2 * (2 * KT * 4 * 1024);  // two buffers of half an image (both slices); the key scales are static LDS
     static DevOnce once;
     static int n_cu[64];  // compute units per device: the persistent grid (one workgroup per CU)
@@ -658,9 +659,9 @@ static int launch_attn_core8_kt(AttnCore8Args a, int BH, hipStream_t s) {
 #ifndef EGOEGO_CORE4
 #define EGOEGO_CORE4 0
 #endif
-template <int KT, bool O8>
+template <int KT, bool O8, bool RAG>
 static int launch_attn_core8w_kt(AttnCore8Args a, int BH, hipStream_t s) {
-    auto kern = attn_core_i8w_kernel<KT, O8>;
+    auto kern = attn_core_i8w_kernel<KT, O8, RAG>;
     constexpr int smem = attn_core8w_smem_bytes<KT>();
     static DevOnce once;
     static int n_cu[64];  // compute units per device: the persistent grid (one workgroup per CU)
@@ -678,11 +679,12 @@ static int launch_attn_core8w_kt(AttnCore8Args a, int BH, hipStream_t s) {
     HIP_TRY(hipGetLastError());
     return 0;
 }
+template <bool RAG>
 static int launch_attn_core8(const AttnCore8Args& a, int KT, int BH, hipStream_t s) {
     // (only windows of 129..224 tokens take this path: seven key tiles; shorter ones run the one-kernel layer or the split-bf16 core)
     if (KT != 7) return fail(EGOEGO_E_INVALID, "unsupported key-tile count %d", KT);
-    if (EGOEGO_CORE4) return a.o8 ? launch_attn_core8_kt<7, true>(a, BH, s) : launch_attn_core8_kt<7, false>(a, BH, s);
-    return a.o8 ? launch_attn_core8w_kt<7, true>(a, BH, s) : launch_attn_core8w_kt<7, false>(a, BH, s);
+    if (EGOEGO_CORE4) return a.o8 ? launch_attn_core8_kt<7, true, RAG>(a, BH, s) : launch_attn_core8_kt<7, false, RAG>(a, BH, s);
+    return a.o8 ? launch_attn_core8w_kt<7, true, RAG>(a, BH, s) : launch_attn_core8w_kt<7, false, RAG>(a, BH, s);
 }
 
 // ------------------------------------------------------------------------------------ the step
@@ -690,6 +692,8 @@ struct StepIO {
     StepState* state;       // multi-step loops: the device-resident step state (nullptr: single step, timesteps from t_idx)
     const int* ts;          // explicit timestep list of a strided sampler or nullptr
     const float* row_mask;  // packed [Mp] or nullptr
+    const int32_t* lens;    // ragged single step: per-window frame counts [B] (loops: StepState::lens); nullptr: every window holds T frames
+    bool ragged;            // per-window lengths and / or Philox ids: the attention kernels and the posterior epilogue run their ragged instantiations
     int stop_layer, stop_stage;  // debug early exit (-1: run everything)
     bool run_out;
     OutParams out;
@@ -697,7 +701,7 @@ struct StepIO {
 
 // One denoiser pass over windows [w0, w0 + nw).  Token rows of a chunk are contiguous, so a chunk is just
 // a token-block offset for the GEMMs and a (batch, head) offset for attention.
-template <int NP>
+template <int NP, bool RAG>
 static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, const StepIO& io, hipStream_t s, int w0,
                         int nw) {
     const int H = c->H, HD = c->HD;
@@ -754,7 +758,10 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
         // (the split-bf16 projection epilogues place whole 32-row tiles: they only ever run on aligned geometries, Lr == Lp)
         EpiQK<NP> eqk{L.b_qkv, w.Q, w.K, w.qkv_plane, 1.0f / sqrtf((float)c->cfg.d_k), g.Lp, H, HD, g.Mvalid};
         EpiV<NP> ev{L.b_qkv, w.V, w.qkv_plane, g.Lp, H, HD, g.Mvalid};
-        AttnArgs aa{w.Q, w.K, w.V, w.qkv_plane, w.O, w.o_plane, HD / 16, H, g.L, w0 * H};
+        // (ragged: the lengths come from the step state in a loop — a captured step must not hold the caller's pointer — else from the call)
+        const int32_t* const lens = RAG && !io.state ? io.lens : nullptr;
+        const StepState* const lstate = RAG ? io.state : nullptr;
+        AttnArgs aa{w.Q, w.K, w.V, w.qkv_plane, w.O, w.o_plane, HD / 16, H, g.L, w0 * H, lens, lstate};
         // the fused kernel has one workgroup per (window, head): below ~one workgroup per CU the unfused pair
         // (12 projection blocks per window) spreads the same work over more CUs
         const bool i8 = NP == 2 && prec_i8(c);
@@ -777,14 +784,15 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
             if (fc8) {
                 al.o8 = w.O8; al.o8_plane = w.o_plane; al.o_scale = w.O_scale;
             }
+            al.lens = lens; al.state = lstate;
             static DevOnce once;
             if (once.pending()) {
-                HIP_TRY(allow_smem(attn_layer_i8w_kernel, AW_DYN_SMEM_BYTES));
-                HIP_TRY(allow_smem(attn_layer_i8h_kernel, AL_SMEM_BYTES));
-                HIP_TRY(allow_smem(attn_proj_i8_kernel, ATTN_PROJ_SMEM));
-                HIP_TRY(allow_smem(attn_core_s_kernel, ATTN_CORE_S_SMEM));
-                HIP_TRY(allow_smem(attn_proj6_i8_kernel, ATTN_PROJ6_SMEM));
-                HIP_TRY(allow_smem(attn_proj2_i8_kernel, ATTN_PROJ_SMEM));
+                HIP_TRY(allow_smem(attn_layer_i8w_kernel<RAG>, AW_DYN_SMEM_BYTES));
+                HIP_TRY(allow_smem(attn_layer_i8h_kernel<RAG>, AL_SMEM_BYTES));
+                HIP_TRY(allow_smem(attn_proj_i8_kernel<RAG>, ATTN_PROJ_SMEM));
+                HIP_TRY(allow_smem(attn_core_s_kernel<RAG>, ATTN_CORE_S_SMEM));
+                HIP_TRY(allow_smem(attn_proj6_i8_kernel<RAG>, ATTN_PROJ6_SMEM));
+                HIP_TRY(allow_smem(attn_proj2_i8_kernel<RAG>, ATTN_PROJ_SMEM));
                 once.done();
             }
             // the projections as three workgroups per (window, head) + a core launch while they fit the chip at once (attn_split_i8.h);
@@ -793,38 +801,38 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
                 const AttnSplitBufs sb{w.att_img, w.sq8, w.sk8, (float*)w.V};
                 c->last_kernel[EGOEGO_K_QKV] = "attn_proj6_i8_kernel";
                 c->last_kernel[EGOEGO_K_ATTN] = "attn_core_s_kernel";
-                attn_proj6_i8_kernel<<<dim3(nw * H * 6), dim3(256), ATTN_PROJ6_SMEM, s>>>(al, sb);
+                attn_proj6_i8_kernel<RAG><<<dim3(nw * H * 6), dim3(256), ATTN_PROJ6_SMEM, s>>>(al, sb);
                 HIP_TRY(hipGetLastError());
-                attn_core_s_kernel<<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
+                attn_core_s_kernel<RAG><<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
             } else if (w.att_img && nw * H * 3 <= ATTN_SPLIT_MAX_BLOCKS) {
                 const AttnSplitBufs sb{w.att_img, w.sq8, w.sk8, (float*)w.V};
                 c->last_kernel[EGOEGO_K_QKV] = "attn_proj_i8_kernel";
                 c->last_kernel[EGOEGO_K_ATTN] = "attn_core_s_kernel";
-                attn_proj_i8_kernel<<<dim3(nw * H * 3), dim3(512), ATTN_PROJ_SMEM, s>>>(al, sb);
+                attn_proj_i8_kernel<RAG><<<dim3(nw * H * 3), dim3(512), ATTN_PROJ_SMEM, s>>>(al, sb);
                 HIP_TRY(hipGetLastError());
-                attn_core_s_kernel<<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
+                attn_core_s_kernel<RAG><<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
             } else if (w.att_img && nw * H * 2 <= ATTN_SPLIT2_MAX_BLOCKS) {
                 const AttnSplitBufs sb{w.att_img, w.sq8, w.sk8, (float*)w.V};
                 c->last_kernel[EGOEGO_K_QKV] = "attn_proj2_i8_kernel";
                 c->last_kernel[EGOEGO_K_ATTN] = "attn_core_s_kernel";
-                attn_proj2_i8_kernel<<<dim3(nw * H * 2), dim3(512), ATTN_PROJ_SMEM, s>>>(al, sb);
+                attn_proj2_i8_kernel<RAG><<<dim3(nw * H * 2), dim3(512), ATTN_PROJ_SMEM, s>>>(al, sb);
                 HIP_TRY(hipGetLastError());
-                attn_core_s_kernel<<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
+                attn_core_s_kernel<RAG><<<dim3(nw * H), dim3(512), ATTN_CORE_S_SMEM, s>>>(al, sb);
             } else
             // up to 24 windows x 4 heads: two workgroups per (window, head), half the queries each (attn_layer_i8h.h)
             if (nw * H * 2 <= ATTN_HALF_MAX_BLOCKS) {
                 c->last_kernel[EGOEGO_K_QKV] = c->last_kernel[EGOEGO_K_ATTN] = "attn_layer_i8h_kernel";
-                attn_layer_i8h_kernel<<<dim3(nw * H * 2), dim3(512), AL_SMEM_BYTES, s>>>(al);
+                attn_layer_i8h_kernel<RAG><<<dim3(nw * H * 2), dim3(512), AL_SMEM_BYTES, s>>>(al);
             } else {
                 c->last_kernel[EGOEGO_K_QKV] = c->last_kernel[EGOEGO_K_ATTN] = "attn_layer_i8w_kernel";
-                attn_layer_i8w_kernel<<<dim3(nw * H), dim3(512), AW_DYN_SMEM_BYTES, s>>>(al);
+                attn_layer_i8w_kernel<RAG><<<dim3(nw * H), dim3(512), AW_DYN_SMEM_BYTES, s>>>(al);
             }
             HIP_TRY(hipGetLastError());
         } else if (fused_attn) {
             // --- fused: Q/K/V projections of one (window, head) + its attention (TM:71-88)
             ProfScope ps(c, EGOEGO_K_QKV, s);
             GemmOperands go{L.w_qkv, (size_t)3 * HD * N_MODEL, w.hA, w.h_plane, N_MODEL / 16, 3 * HD / BLK_A_F, tb_a, 0 EG_DBG(, g_ablate, g_trace)};
-            auto kern = qkv_attn_kernel<CfgA<NP>, EpiQK<NP>, CfgAV<NP>, EpiV<NP>, CfgQ<NP>, 4, NP>;
+            auto kern = qkv_attn_kernel<CfgA<NP>, EpiQK<NP>, CfgAV<NP>, EpiV<NP>, CfgQ<NP>, 4, NP, RAG>;
             constexpr int smem = CfgA<NP>::SMEM_BYTES > 2 * 4 * NP * 4096 ? CfgA<NP>::SMEM_BYTES : 2 * 4 * NP * 4096;
             static DevOnce once;
             if (once.pending()) {
@@ -869,8 +877,9 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
                     if (fc8) {
                         ca.o8 = w.O8; ca.o8_plane = w.o_plane; ca.o_scale = w.O_scale;
                     }
+                    ca.lens = lens; ca.state = lstate;
                     c->last_kernel[EGOEGO_K_ATTN] = EGOEGO_CORE4 ? "attn_core_i8_kernel" : "attn_core_i8w_kernel";
-                    if (int r = launch_attn_core8(ca, g.KT, g.B * H, s)) return r;
+                    if (int r = launch_attn_core8<RAG>(ca, g.KT, g.B * H, s)) return r;
                 }
             } else if (i8 && !dbg_qkv) {
                 // short windows: int8-slice projections feeding the split-bf16 attention core
@@ -903,7 +912,7 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
             if (!core8) {
                 ProfScope ps(c, EGOEGO_K_ATTN, s);
                 c->last_kernel[EGOEGO_K_ATTN] = (NP == 2 && g.KT == 7 && !EGOEGO_ATTN_WG4 && nw * H >= 256) ? "attn8_kernel" : "attn_kernel";
-                if (int r = launch_attn<NP>(aa, g.KT, nw * H, s)) return r;
+                if (int r = launch_attn<NP, RAG>(aa, g.KT, nw * H, s)) return r;
             }
         }
         if (last_dbg && io.stop_stage == EGOEGO_DBG_ATTN_OUT) return 0;
@@ -1092,14 +1101,14 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
     if (io.run_out) {
         ProfScope ps(c, EGOEGO_K_OUT, s);
         if (NP == 2 && direct_io) {
-            OutArgs oa{w.hA, w.h_plane, c->w_out, (size_t)c->NOUT * N_MODEL, EpiOut<2>{io.out},
+            OutArgsT<RAG> oa{w.hA, w.h_plane, c->w_out, (size_t)c->NOUT * N_MODEL, EpiOut<2, RAG>{io.out},
                        w.hA8, w.h_plane, w.hA_scale, c->w_out_8, (size_t)c->NOUT * N_MODEL, c->s_out};
             c->last_kernel[EGOEGO_K_OUT] = "out_kernel";
-            if (int r = act8_only ? launch_out_tt<1, true>(oa, rows, s) : launch_out_tt<1, false>(oa, rows, s)) return r;
+            if (int r = act8_only ? launch_out_tt<1, true, RAG>(oa, rows, s) : launch_out_tt<1, false, RAG>(oa, rows, s)) return r;
         } else if (NP == 2 && act8_only) {
             // the last layer's output exists as int8 rows only: linear_out on int8 slices, 256 features x 128 tokens per eight-wave workgroup
             GemmOperands go{(const __bf16*)c->w_out_8, (size_t)c->NOUT * N_MODEL / 2, (const __bf16*)w.hA8, w.h_plane / 2, N_MODEL / 32, 1, rows / 128, row0 / 128 EG_DBG(, g_ablate, g_trace)};
-            auto kern = gemm_i8_kernel<AW8K, EpiOut<2>>;
+            auto kern = gemm_i8_kernel<AW8K, EpiOut<2, RAG>>;
             // (after the main loop the ring's LDS holds the block's x rows: EpiOut::run_block)
             const int out_smem = std::max((int)AW8K::SMEM_BYTES, AW8K::BT * c->cfg.d_feats * 4 + 16);
             static DevOnce once;
@@ -1109,11 +1118,11 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
             }
             if (out_smem > 160 * 1024) return fail(EGOEGO_E_INVALID, "d_feats too large for the linear_out kernel's LDS staging");
             c->last_kernel[EGOEGO_K_OUT] = "gemm_i8_kernel:EpiOut";
-            kern<<<dim3(go.ntb), dim3(AW8K::NT), out_smem, s>>>(go, c->s_out, w.hA_scale, EpiOut<2>{io.out});
+            kern<<<dim3(go.ntb), dim3(AW8K::NT), out_smem, s>>>(go, c->s_out, w.hA_scale, EpiOut<2, RAG>{io.out});
             HIP_TRY(hipGetLastError());
         } else {
             GemmOperands go{c->w_out, (size_t)c->NOUT * N_MODEL, w.hA, w.h_plane, N_MODEL / 16, 1, tb_c, t0_c EG_DBG(, g_ablate, g_trace)};
-            EpiOut<NP> e{io.out};
+            EpiOut<NP, RAG> e{io.out};
             if (tb_c <= SMALL_GRID) {
                 GemmOperands gs{c->w_out, (size_t)c->NOUT * N_MODEL, w.hA, w.h_plane, N_MODEL / 16, 1, rows / 64, row0 / 64 EG_DBG(, g_ablate, g_trace)};
                 c->last_kernel[EGOEGO_K_OUT] = "gemm_kernel:EpiOut<CfgC2>";
@@ -1129,7 +1138,8 @@ static int run_chunk_np(egoego_ctx* c, const Geometry& g, const Workspace& w, co
 
 template <int NP>
 static int run_denoiser_np(egoego_ctx* c, const Geometry& g, const Workspace& w, const StepIO& io, hipStream_t s) {
-    return run_chunk_np<NP>(c, g, w, io, s, 0, g.B);
+    // uniform calls launch the instantiations they always did; a ragged call its own (per-window key counts)
+    return io.ragged ? run_chunk_np<NP, true>(c, g, w, io, s, 0, g.B) : run_chunk_np<NP, false>(c, g, w, io, s, 0, g.B);
 }
 
 static int run_denoiser(egoego_ctx* c, const Geometry& g, const Workspace& w, const StepIO& io, hipStream_t s) {
@@ -1417,8 +1427,12 @@ size_t egoego_workspace_bytes(const egoego_ctx* c, int B, int T) {
     return w.total;
 }
 
-int egoego_denoise(egoego_ctx* c, const float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
-                   float* d_out, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
+// (ends the extern "C" block for the shared bodies of the uniform and the ragged entry points)
+}
+
+// d_lengths: per-window frame counts (egoego_*_ragged) or nullptr; d_window_ids: per-window Philox ids or nullptr
+static int denoise_impl(egoego_ctx* c, const float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
+                        const int32_t* d_lengths, float* d_out, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
     if (int r = check_ready(c, false)) return r;
     if (!d_x || !d_xc || !d_t || !d_out) return fail(EGOEGO_E_INVALID, "null tensor pointer");
     hipStream_t s = (hipStream_t)stream;
@@ -1435,12 +1449,14 @@ int egoego_denoise(egoego_ctx* c, const float* d_x, const float* d_xc, const int
     base_out_params(c, g, w, io.out);
     io.out.mode = 0;
     io.out.out_raw = d_out;
+    io.lens = d_lengths;
+    io.ragged = d_lengths != nullptr;
     return run_denoiser(c, g, w, io, s);
 }
 
-int egoego_p_sample(egoego_ctx* c, float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
-                    const float* d_noise, int noise_mode, uint64_t seed, int64_t window_offset, int clip_denoised,
-                    int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
+static int p_sample_impl(egoego_ctx* c, float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
+                         const int32_t* d_lengths, const int64_t* d_window_ids, const float* d_noise, int noise_mode, uint64_t seed,
+                         int64_t window_offset, int clip_denoised, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
     if (int r = check_ready(c, true)) return r;
     if (!d_x || !d_xc || !d_t) return fail(EGOEGO_E_INVALID, "null tensor pointer");
     if (noise_mode == EGOEGO_NOISE_INJECTED && !d_noise) return fail(EGOEGO_E_INVALID, "noise_mode INJECTED needs d_noise");
@@ -1463,7 +1479,10 @@ int egoego_p_sample(egoego_ctx* c, float* d_x, const float* d_xc, const int64_t*
     io.out.noise_mode = noise_mode;
     io.out.seed = seed;
     io.out.window_offset = window_offset;
+    io.out.window_ids = d_window_ids;
     io.out.clip = clip_denoised ? 1 : 0;
+    io.lens = d_lengths;
+    io.ragged = d_lengths != nullptr || d_window_ids != nullptr;
     return run_denoiser(c, g, w, io, s);
 }
 
@@ -1479,11 +1498,14 @@ struct StepCall {
     const float* prefix;
     uint64_t seed;
     int64_t window_offset;
+    const int32_t* lens;        // ragged calls: per-window frame counts / Philox ids (nullptr: uniform / window_offset + b)
+    const int64_t* window_ids;
 };
 
 static int run_steps(egoego_ctx* c, const Geometry& g, const Workspace& w, StepIO& io, const StepKey& key, const StepCall& call,
                      int n_steps, hipStream_t s) {
-    k_state_init<<<1, 1, 0, s>>>(w.state, call.t_start, call.x, call.noise, call.prefix, call.seed, call.window_offset);
+    k_state_init<<<1, 1, 0, s>>>(w.state, call.t_start, call.x, call.noise, call.prefix, call.seed, call.window_offset, call.lens,
+                                call.window_ids);
     HIP_TRY(hipGetLastError());
     io.state = w.state;
     io.ts = key.ddim ? w.step_ts : nullptr;
@@ -1533,9 +1555,10 @@ static int run_steps(egoego_ctx* c, const Geometry& g, const Workspace& w, StepI
     return 0;
 }
 
-int egoego_sample_loop(egoego_ctx* c, float* d_x, const float* d_xc, int t_start, int n_steps, const float* d_noise,
-                       int noise_mode, uint64_t seed, int64_t window_offset, const float* d_prefix, int prefix_len,
-                       const float* d_row_mask, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
+static int sample_loop_impl(egoego_ctx* c, float* d_x, const float* d_xc, int t_start, int n_steps, const float* d_noise,
+                            int noise_mode, uint64_t seed, int64_t window_offset, const float* d_prefix, int prefix_len,
+                            const float* d_row_mask, const int32_t* d_lengths, const int64_t* d_window_ids, int B, int T, void* d_ws,
+                            size_t ws_bytes, void* stream) {
     if (int r = check_ready(c, true)) return r;
     if (!d_x || !d_xc) return fail(EGOEGO_E_INVALID, "null tensor pointer");
     if (t_start < 0 || t_start >= c->S || n_steps < 0 || n_steps > t_start + 1)
@@ -1559,9 +1582,51 @@ int egoego_sample_loop(egoego_ctx* c, float* d_x, const float* d_xc, int t_start
     io.out.noise_mode = noise_mode;
     io.out.prefix_len = d_prefix ? prefix_len : 0;
     io.out.step_elems = (size_t)B * T * c->D;
-    const StepKey key{B, T, 1, noise_mode, io.out.prefix_len, 1, 0, d_row_mask ? 1 : 0, d_ws};
-    const StepCall call{t_start, d_x, noise_mode == EGOEGO_NOISE_INJECTED ? d_noise : nullptr, d_prefix, seed, window_offset};
+    // The lengths and ids reach the kernels through the step state: one captured ragged step serves every later ragged call of this
+    // shape, whatever its arrays.  Arrays against none selects other kernel instantiations, so it is part of the key.
+    io.ragged = d_lengths != nullptr || d_window_ids != nullptr;
+    const StepKey key{B, T, 1, noise_mode, io.out.prefix_len, 1, 0, d_row_mask ? 1 : 0, io.ragged ? 1 : 0, d_ws};
+    const StepCall call{t_start, d_x, noise_mode == EGOEGO_NOISE_INJECTED ? d_noise : nullptr, d_prefix, seed, window_offset, d_lengths,
+                        d_window_ids};
     return run_steps(c, g, w, io, key, call, n_steps, s);
+}
+
+extern "C" {
+
+int egoego_denoise(egoego_ctx* c, const float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
+                   float* d_out, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
+    return denoise_impl(c, d_x, d_xc, d_t, d_row_mask, nullptr, d_out, B, T, d_ws, ws_bytes, stream);
+}
+int egoego_denoise_ragged(egoego_ctx* c, const float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
+                          const int32_t* d_lengths, float* d_out, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
+    return denoise_impl(c, d_x, d_xc, d_t, d_row_mask, d_lengths, d_out, B, T, d_ws, ws_bytes, stream);
+}
+
+int egoego_p_sample(egoego_ctx* c, float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
+                    const float* d_noise, int noise_mode, uint64_t seed, int64_t window_offset, int clip_denoised,
+                    int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
+    return p_sample_impl(c, d_x, d_xc, d_t, d_row_mask, nullptr, nullptr, d_noise, noise_mode, seed, window_offset, clip_denoised, B, T,
+                         d_ws, ws_bytes, stream);
+}
+int egoego_p_sample_ragged(egoego_ctx* c, float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
+                           const int32_t* d_lengths, const int64_t* d_window_ids, const float* d_noise, int noise_mode, uint64_t seed,
+                           int64_t window_offset, int clip_denoised, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
+    return p_sample_impl(c, d_x, d_xc, d_t, d_row_mask, d_lengths, d_window_ids, d_noise, noise_mode, seed, window_offset, clip_denoised,
+                         B, T, d_ws, ws_bytes, stream);
+}
+
+int egoego_sample_loop(egoego_ctx* c, float* d_x, const float* d_xc, int t_start, int n_steps, const float* d_noise,
+                       int noise_mode, uint64_t seed, int64_t window_offset, const float* d_prefix, int prefix_len,
+                       const float* d_row_mask, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
+    return sample_loop_impl(c, d_x, d_xc, t_start, n_steps, d_noise, noise_mode, seed, window_offset, d_prefix, prefix_len, d_row_mask,
+                            nullptr, nullptr, B, T, d_ws, ws_bytes, stream);
+}
+int egoego_sample_loop_ragged(egoego_ctx* c, float* d_x, const float* d_xc, int t_start, int n_steps, const float* d_noise,
+                              int noise_mode, uint64_t seed, int64_t window_offset, const float* d_prefix, int prefix_len,
+                              const float* d_row_mask, const int32_t* d_lengths, const int64_t* d_window_ids, int B, int T,
+                              void* d_ws, size_t ws_bytes, void* stream) {
+    return sample_loop_impl(c, d_x, d_xc, t_start, n_steps, d_noise, noise_mode, seed, window_offset, d_prefix, prefix_len, d_row_mask,
+                            d_lengths, d_window_ids, B, T, d_ws, ws_bytes, stream);
 }
 
 int egoego_ddim_loop(egoego_ctx* c, float* d_x, const float* d_xc, const int32_t* ts, int n, float eta, const float* d_noise,
@@ -1619,8 +1684,8 @@ int egoego_ddim_loop(egoego_ctx* c, float* d_x, const float* d_xc, const int32_t
     io.out.noise_mode = eta > 0.f ? noise_mode : EGOEGO_NOISE_NONE;
     io.out.ddim_tab = w.step_tab;
     io.out.step_elems = (size_t)B * T * c->D;
-    const StepKey key{B, T, 2, io.out.noise_mode, 0, 1, 1, 0, d_ws};
-    const StepCall call{0, d_x, io.out.noise_mode == EGOEGO_NOISE_INJECTED ? d_noise : nullptr, nullptr, seed, window_offset};
+    const StepKey key{B, T, 2, io.out.noise_mode, 0, 1, 1, 0, 0, d_ws};
+    const StepCall call{0, d_x, io.out.noise_mode == EGOEGO_NOISE_INJECTED ? d_noise : nullptr, nullptr, seed, window_offset, nullptr, nullptr};
     return run_steps(c, g, w, io, key, call, n, s);
 }
 

@@ -1223,11 +1223,12 @@ struct OutParams {
     // multi-step loops: everything that changes from call to call or from step to step lives in device memory (the
     // step state, pointwise.h), so that ONE captured step replays for every timestep, every chain and every caller
     // buffer: state->out_step - 1 is the index of the running step (selects the timestep, the injected-noise slice
-    // and the DDIM table row); x / noise / prefix / seed / window_offset come from it too.  nullptr: single step.
+    // and the DDIM table row); x / noise / prefix / seed / window_offset / window_ids come from it too.  nullptr: single step.
     StepState* state;
     const int* ts;         // explicit timestep list or nullptr
     size_t step_elems;     // B*T*D: stride between the injected-noise slices of consecutive steps
     int Lp, T, B, D, DP;
+    const int64_t* window_ids;  // (EpiOut<NP, true> only) [B] per-window Philox ids or nullptr: window_offset + b (single step)
 };
 
 // what a launch of the out kernel reads from the step state (or, for a single step, from OutParams)
@@ -1237,6 +1238,7 @@ struct OutDyn {
     const float* prefix;
     uint64_t seed;
     int64_t window_offset;
+    const int64_t* window_ids;
     float a_prev, dir, sig;  // DDIM coefficients of this step
 };
 
@@ -1248,7 +1250,8 @@ typedef __attribute__((address_space(3))) f32x2 LdsF2;
 typedef __attribute__((address_space(3))) f32x4 LdsF4;
 typedef __attribute__((address_space(1))) f32x2 GlbF2;
 typedef __attribute__((address_space(1))) f32x4 GlbF4;
-template <int NP>
+// IDS: the per-window Philox ids of ragged calls are read (a uniform call launches the IDS = false instantiations: the code it always ran)
+template <int NP, bool IDS = false>
 struct EpiOut {
     OutParams p;
     // Kernels whose workgroup owns ALL the (padded) output features of its token rows may stage the x rows through LDS (run_block)
@@ -1288,7 +1291,12 @@ struct EpiOut {
                         nz[c + 1] = v.y;
                     }
             } else if (p.noise_mode == 1) {
-                philox_normal4(d.seed, (uint32_t)(f >> 2), (uint32_t)frame, (uint32_t)(d.window_offset + b), (uint32_t)t, nz);
+                // (a compacted or reordered set of windows keeps each window's own stream through its id)
+                int64_t wid = d.window_offset + b;
+                if constexpr (IDS) {
+                    if (d.window_ids) wid = d.window_ids[b];
+                }
+                philox_normal4(d.seed, (uint32_t)(f >> 2), (uint32_t)frame, (uint32_t)wid, (uint32_t)t, nz);
             }
         }
         float xn[4];
@@ -1326,7 +1334,7 @@ struct EpiOut {
 
     // what this launch reads from the step state (or from OutParams for a single step)
     EG_D OutDyn dynamic(int& step, int& t_loop) const {
-        OutDyn d{p.x, p.noise, p.prefix, p.seed, p.window_offset, 1.0f, 0.f, 0.f};
+        OutDyn d{p.x, p.noise, p.prefix, p.seed, p.window_offset, p.window_ids, 1.0f, 0.f, 0.f};
         step = 0;
         t_loop = 0;
         if (p.state) {
@@ -1337,6 +1345,7 @@ struct EpiOut {
             d.prefix = p.prefix_len ? p.state->prefix : nullptr;
             d.seed = p.state->seed;
             d.window_offset = p.state->window_offset;
+            if constexpr (IDS) d.window_ids = p.state->window_ids;
             // no block of THIS launch reads embed_step; the next step's embed kernel does
             if (blockIdx.x == 0 && threadIdx.x == 0) p.state->embed_step = step + 1;
         }

@@ -151,7 +151,7 @@ __global__ void k_convert_t(const int64_t* __restrict__ t, int* __restrict__ out
 
 // (Re)arm the step state (gemm.h StepState) at the start of a multi-step call: one thread.
 __global__ void k_state_init(StepState* __restrict__ st, int t_start, float* x, const float* noise, const float* prefix, uint64_t seed,
-                             int64_t window_offset) {
+                             int64_t window_offset, const int32_t* lens, const int64_t* window_ids) {
     st->embed_step = 0;
     st->t_start = t_start;
     st->out_step = 0;
@@ -161,6 +161,8 @@ __global__ void k_state_init(StepState* __restrict__ st, int t_start, float* x, 
     st->prefix = prefix;
     st->seed = seed;
     st->window_offset = window_offset;
+    st->lens = lens;
+    st->window_ids = window_ids;
 }
 
 // Padding mask [B][T+1] -> one multiplier per padded token row.

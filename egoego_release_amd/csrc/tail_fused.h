@@ -638,12 +638,13 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 ? 2 : 1)) void embed_kernel(Emb
     e.template run<FT, TT>(acc, wave * FT * 32, (int)blockIdx.x * 32 * TT, lane, wave, 0, smem);
 }
 
-struct OutArgs {
+template <bool IDS = false>
+struct OutArgsT {
     const __bf16* h;   // last layer's output [Mp][512]
     size_t h_plane;
     const __bf16* w;   // [256][512] (rows >= d_feats zero)
     size_t w_plane;
-    EpiOut<2> epi;
+    EpiOut<2, IDS> epi;
     // I8 builds (precision 9's product path: the last layer hands its output over as int8 rows only): the same contraction on int8
     // slices — the rows with one scale each, linear_out's weights with one scale per output row
     const int8_t* h8;
@@ -655,8 +656,8 @@ struct OutArgs {
 };
 // FS = 2: grids of at most 128 token blocks (half the CUs) split the 256 output features over two workgroups per token block
 // (a wave then owns 32 features): the posterior epilogue is elementwise, so nothing crosses the split.
-template <int TT, int FS, bool I8 = false>
-__global__ __launch_bounds__(256, 1) void out_kernel(OutArgs a) {
+template <int TT, int FS, bool I8 = false, bool IDS = false>
+__global__ __launch_bounds__(256, 1) void out_kernel(OutArgsT<IDS> a) {
     constexpr int FT = 2 / FS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = wave_id_uniform(), lane = threadIdx.x & 63;

@@ -5,6 +5,7 @@ step happens in the HIP library.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -14,6 +15,48 @@ TR = "denoise_fn.motion_transformer."
 
 def _f32c(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def check_lengths(lengths, B, T, prefix_len=0):
+    """Per-window frame counts of a ragged call -> an int32 host array [B], or the caller's CUDA tensor as given.
+    Host values are validated here, before anything is launched: each in 1..T (T: the padded length) and none below
+    `prefix_len` (the in-painted prefix must lie inside every window).  A CUDA tensor is taken as given, like
+    evaluate._lengths does, so that no call waits for the device: its values are the caller's responsibility."""
+    if isinstance(lengths, torch.Tensor) and lengths.device.type == "cuda":
+        if lengths.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise ValueError(f"lengths must be an integer tensor, got {lengths.dtype}")
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(f"lengths {tuple(lengths.shape)}: [{B}] expected")
+        return lengths
+    a = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths)
+    if a.shape != (B,):
+        raise ValueError(f"lengths {tuple(a.shape)}: [{B}] expected")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"lengths must be integers, got {a.dtype}")
+    a = a.astype(np.int64)
+    if a.min() < 1 or a.max() > T:
+        raise ValueError(f"lengths span {int(a.min())}..{int(a.max())}: 1..{T} (the padded T) expected")
+    if prefix_len > a.min():
+        raise ValueError(f"prefix of {prefix_len} frames, but lengths span {int(a.min())}..{int(a.max())}: the prefix must fit every window")
+    return a.astype(np.int32)
+
+
+def check_window_ids(window_ids, B):
+    """Per-window Philox ids of a ragged call -> an int64 host array [B], or the caller's CUDA tensor as given."""
+    if isinstance(window_ids, torch.Tensor) and window_ids.device.type == "cuda":
+        if window_ids.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise ValueError(f"window_ids must be an integer tensor, got {window_ids.dtype}")
+        if tuple(window_ids.shape) != (B,):
+            raise ValueError(f"window_ids {tuple(window_ids.shape)}: [{B}] expected")
+        return window_ids
+    a = np.asarray(window_ids.cpu() if isinstance(window_ids, torch.Tensor) else window_ids)
+    if a.shape != (B,):
+        raise ValueError(f"window_ids {tuple(a.shape)}: [{B}] expected")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"window_ids must be integers, got {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
+        raise ValueError(f"window_ids span {int(a.min())}..{int(a.max())}: the Philox counter word holds 0..2^32-1")
+    return a.astype(np.int64)
 
 
 class HipEngine:
@@ -136,36 +179,64 @@ class HipEngine:
         m = row_mask.reshape(B, T + 1).to(device=self.device, dtype=torch.float32).contiguous()
         return m, m.data_ptr()
 
+    def _ragged(self, lengths, window_ids, B, T, prefix_len=0):
+        """-> (lengths int32 device tensor | None, window_ids int64 device tensor | None); raises ValueError on bad host values
+        before anything is launched.  The tensors must stay referenced until the call is enqueued (the stream orders the rest)."""
+        lt = it = None
+        if lengths is not None:
+            lt = check_lengths(lengths, B, T, prefix_len)
+            lt = (lt if isinstance(lt, torch.Tensor) else torch.from_numpy(lt)).to(device=self.device, dtype=torch.int32).contiguous()
+        if window_ids is not None:
+            it = check_window_ids(window_ids, B)
+            it = (it if isinstance(it, torch.Tensor) else torch.from_numpy(it)).to(device=self.device, dtype=torch.int64).contiguous()
+        return lt, it
+
     # ------------------------------------------------------------------ entry points
-    def denoise(self, x, x_cond, t, row_mask=None):
+    # lengths (every entry point below): per-window frame counts [B], a host sequence or a CUDA int tensor — window b attends over
+    # its first lengths[b] frames only; its rows past them come back unspecified (finite).  window_ids: per-window Philox ids [B].
+    def denoise(self, x, x_cond, t, row_mask=None, lengths=None):
         B, T, D = x.shape
+        lt, _ = self._ragged(lengths, None, B, T)
         out = torch.empty_like(x)
         ws, n = self.workspace(B, T)
         m, mp = self._mask(row_mask, B, T)
+        if lt is not None:
+            _lib.check(self.lib.egoego_denoise_ragged(self._ctx, self._chk(x), self._chk(x_cond, x.shape),
+                                                      self._chk(t, (B,), torch.int64), mp, lt.data_ptr(), self._chk(out), B, T, ws, n,
+                                                      self._stream()))
+            return out
         _lib.check(self.lib.egoego_denoise(self._ctx, self._chk(x), self._chk(x_cond, x.shape),
                                            self._chk(t, (B,), torch.int64), mp, self._chk(out), B, T, ws, n,
                                            self._stream()))
         return out
 
     def p_sample_(self, x, x_cond, t, noise=None, row_mask=None, clip_denoised=True, noise_mode=None, seed=0,
-                  window_offset=0):
+                  window_offset=0, lengths=None, window_ids=None):
         """In-place x <- p_sample(x, t, x_cond)."""
         B, T, D = x.shape
+        lt, it = self._ragged(lengths, window_ids, B, T)
         if noise_mode is None:
             noise_mode = _lib.NOISE_INJECTED if noise is not None else _lib.NOISE_NONE
         ws, n = self.workspace(B, T)
         m, mp = self._mask(row_mask, B, T)
         npnt = self._chk(noise, x.shape) if noise is not None else None
+        if lt is not None or it is not None:
+            _lib.check(self.lib.egoego_p_sample_ragged(self._ctx, self._chk(x), self._chk(x_cond, x.shape),
+                                                       self._chk(t, (B,), torch.int64), mp, lt.data_ptr() if lt is not None else None,
+                                                       it.data_ptr() if it is not None else None, npnt, noise_mode, seed, window_offset,
+                                                       1 if clip_denoised else 0, B, T, ws, n, self._stream()))
+            return x
         _lib.check(self.lib.egoego_p_sample(self._ctx, self._chk(x), self._chk(x_cond, x.shape),
                                             self._chk(t, (B,), torch.int64), mp, npnt, noise_mode, seed, window_offset,
                                             1 if clip_denoised else 0, B, T, ws, n, self._stream()))
         return x
 
     def sample_loop_(self, x, x_cond, t_start, n_steps, noise=None, noise_mode=None, seed=0, window_offset=0,
-                     prefix=None, row_mask=None):
+                     prefix=None, row_mask=None, lengths=None, window_ids=None):
         """In-place: n_steps ancestral steps from timestep t_start downwards (row_mask: the padding mask every
         step's denoiser pass applies, [B, 1, T+1] / [B, T+1])."""
         B, T, D = x.shape
+        lt, it = self._ragged(lengths, window_ids, B, T, prefix.shape[1] if prefix is not None else 0)
         if noise_mode is None:
             noise_mode = _lib.NOISE_INJECTED if noise is not None else _lib.NOISE_PHILOX
         ws, n = self.workspace(B, T)
@@ -175,6 +246,12 @@ class HipEngine:
             plen = prefix.shape[1]
             pp = self._chk(prefix, (B, plen, D))
         m, mp = self._mask(row_mask, B, T)
+        if lt is not None or it is not None:
+            _lib.check(self.lib.egoego_sample_loop_ragged(self._ctx, self._chk(x), self._chk(x_cond, x.shape), t_start, n_steps,
+                                                          npnt, noise_mode, seed, window_offset, pp, plen, mp,
+                                                          lt.data_ptr() if lt is not None else None,
+                                                          it.data_ptr() if it is not None else None, B, T, ws, n, self._stream()))
+            return x
         _lib.check(self.lib.egoego_sample_loop(self._ctx, self._chk(x), self._chk(x_cond, x.shape), t_start, n_steps,
                                                npnt, noise_mode, seed, window_offset, pp, plen, mp, B, T, ws, n,
                                                self._stream()))

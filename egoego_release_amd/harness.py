@@ -382,6 +382,148 @@ def full_body_gen_cond_head_pose_sliding_window(model, ds, head_pose, noise=None
                                              parents=parents, window_offset=window_offset, group=group, global_pairs=global_pairs)
 
 
+# ------------------------------------------------------------------------------------------ ragged: many sequences, one batch
+def ragged_window_table(num_frames_per_sequence, seq_len):
+    """The windows the sliding-window loop runs over SEVERAL trajectories of different lengths, grouped by window index: entry k
+    is {'sequences': [s, ...], 'spans': [(first frame, length), ...], 'continues': [bool, ...]} over the sequences that have a
+    k-th window (ascending s) — `spans` as window_spans(num_frames[s], seq_len)[k], `continues`: the sequence has a window k + 1
+    (its window k is then seq_len frames long: only a sequence's last window can be short).  Pure host function.
+    A trajectory without a window (10 frames or fewer) raises ValueError."""
+    per_seq = []
+    for s, n in enumerate(num_frames_per_sequence):
+        spans = window_spans(int(n), seq_len)
+        if not spans:
+            raise ValueError(f"sequence {s} has {int(n)} frames: more than {OVERLAP} are needed for a window")
+        per_seq.append(spans)
+    table = []
+    for k in range(max((len(sp) for sp in per_seq), default=0)):
+        act = [s for s, sp in enumerate(per_seq) if len(sp) > k]
+        table.append({"sequences": act, "spans": [per_seq[s][k] for s in act], "continues": [len(per_seq[s]) > k + 1 for s in act]})
+    return table
+
+
+@torch.no_grad()
+def full_body_gen_cond_head_pose_sliding_window_ragged(model, ds, head_poses, samples_per_sequence=1, noise=None, parents=None,
+                                                        sequence_offset=0, lengths=None):
+    """full_body_gen_cond_head_pose_sliding_window over SEVERAL trajectories of different lengths at once: window index k runs ONCE,
+    as one ragged batch (model/engine `lengths=`), for every (sequence, sample) pair that has a k-th window, instead of once per
+    sequence — the sampler's step costs almost the same for 1 and for 100 windows.
+
+    head_poses: a list of [T_s, 7] tensors (xyz + quaternion w,x,y,z), or a padded [S, Tmax, 7] tensor with `lengths` [S].
+    -> (local axis-angle [S*n, T'max, 22, 3], root [S*n, T'max, 3], out_lengths [S*n] (int64, host)), pair s * n + j = sample j of
+    sequence s, out_lengths = output_frames(T_s, seq_len), zeros past it: evaluate_samples(..., lengths=out_lengths) takes it as is.
+
+    Every batch is padded to seq_len frames; a short (last) window's head poses are padded with its last real frame, so the
+    canonicalisation never meets a zero quaternion, and what the sampler leaves in its padded frames is never read.  Each sequence
+    is stitched by the rule of the one-sequence loop.  Only full windows are followed by another, so the prefix / condition /
+    conversion kernels run unchanged on gathered subsets.
+    Noise: per-step draws are in-kernel Philox keyed by (philox_seed + k; sequence_offset + pair index, ...) — a sequence sampled
+    alone through the one-sequence harness with window_offset = sequence_offset + s * n draws the same stream; `sequence_offset`
+    is also what a sharded caller sets.  noise: a list of that harness's dicts, one per sequence ({'x_all': [n, T_s, D], 'cond':
+    [per window [n, Tw, D]], optionally 'steps': [per window [S, n, Tw, D]]} — in every dict or in none), injects the draws (tests).
+    Unless every step is injected, model.sampling_rng = "torch" is not supported here (one generator cannot be consumed in every sequence's own order): set it to "philox"."""
+    if isinstance(head_poses, torch.Tensor):
+        if lengths is None:
+            raise ValueError("a padded head_poses tensor needs lengths")
+        lens = [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+        if head_poses.dim() != 3 or len(lens) != head_poses.shape[0] or (lens and (min(lens) < 1 or max(lens) > head_poses.shape[1])):
+            raise ValueError(f"head_poses {tuple(head_poses.shape)} with lengths spanning {min(lens, default=0)}..{max(lens, default=0)}")
+        head_poses = [head_poses[i, :n] for i, n in enumerate(lens)]
+    n_smp, n_seq = int(samples_per_sequence), len(head_poses)
+    if n_smp < 1 or n_seq < 1:
+        raise ValueError("at least one sequence and one sample per sequence are needed")
+    if noise is not None and len(noise) != n_seq:
+        raise ValueError(f"noise: one dict per sequence expected ({n_seq}), got {len(noise)}")
+    with_steps = [] if noise is None else ["steps" in d for d in noise]
+    if with_steps and any(with_steps) != all(with_steps):
+        raise ValueError("noise: either every sequence's dict carries 'steps' or none does "
+                         f"(sequences with: {[s for s, w in enumerate(with_steps) if w]})")
+    inject_steps = noise is not None and all(with_steps)
+    if not inject_steps and model.sampling_rng != "philox":  # (the per-step draws are then in-kernel Philox: never silently)
+        raise ValueError(f'sampling_rng="{model.sampling_rng}" is not supported by the ragged sliding-window call: set model.sampling_rng = "philox"')
+    S, seq_len = model.num_timesteps, model.seq_len
+    stride = seq_len - OVERLAP
+    frames = [int(h.shape[0]) for h in head_poses]
+    table = ragged_window_table(frames, seq_len)  # (raises for a sequence without a window)
+    out_len = [output_frames(f, seq_len) for f in frames]
+    P, D = n_seq * n_smp, 198
+    device = model.betas.device
+    job = (n_smp * sum(len(e["sequences"]) for e in table), seq_len, S)
+    eng = model.hip_engine(verify=True, job=job)
+    parents = _parents_of(ds, parents)
+    # every pair's trajectory and x_T, padded so that every window slices seq_len frames: poses by the last real frame, x_T by zeros
+    t_pad = max(frames) + seq_len
+    pose_all = torch.empty(P, t_pad, 7, device=device)
+    x_all = torch.zeros(P, t_pad, D, device=device)
+    for s, h in enumerate(head_poses):
+        h = h.to(device).float()
+        rows = slice(s * n_smp, (s + 1) * n_smp)
+        pose_all[rows, :frames[s]] = h
+        pose_all[rows, frames[s]:] = h[-1]
+        x_all[rows, :frames[s]] = noise[s]["x_all"].to(device).float() if noise is not None else torch.randn(n_smp, frames[s], D, device=device)
+    cm = prep_head_condition_mask(torch.zeros(1, seq_len, D, device=device))
+    t_out = max(out_len)
+    whole_aa = torch.zeros(P, t_out, 22, 3, device=device)
+    whole_root = torch.zeros(P, t_out, 3, device=device)
+    head_last = torch.zeros(P, 1, 3, device=device)  # stitched head position of every pair's last frame so far
+    prefix_all = torch.zeros(P, OVERLAP, D, device=device)
+    for k, ent in enumerate(table):
+        t0 = k * stride
+        pairs = [s * n_smp + j for s in ent["sequences"] for j in range(n_smp)]
+        wlen = [n for (_, n) in ent["spans"] for _ in range(n_smp)]
+        cont = [c for c in ent["continues"] for _ in range(n_smp)]
+        assert all(a == t0 for a, _ in ent["spans"])
+        idx = torch.as_tensor(pairs, device=device)
+        bk = len(pairs)
+        curr_x = x_all[idx, t0:t0 + seq_len].contiguous()
+        cur_jpos = pose_all[idx, t0:t0 + seq_len, :3].contiguous()
+        cur_quat = pose_all[idx, t0:t0 + seq_len, 3:].contiguous()
+        cond = _window_condition_hip(ds, cur_jpos, cur_quat)
+        x_start, recover = cond if cond is not None else _window_condition_torch(ds, cur_jpos, cur_quat)
+        if noise is not None:
+            cn = torch.zeros(bk, seq_len, D, device=device)
+            for i, s in enumerate(ent["sequences"]):
+                cn[i * n_smp:(i + 1) * n_smp, :ent["spans"][i][1]] = noise[s]["cond"][k].to(device).float()
+        else:
+            cn = torch.randn_like(x_start)
+        x_cond = (x_start * (1.0 - cm) + cm * cn).float().contiguous()
+        pfx = prefix_all[idx].contiguous() if k > 0 else None
+        if k == 0:  # (the first window index's conditions shape stage 2 of the plan's measurement)
+            eng = model.hip_engine(verify=True, job=job, conditions=x_cond)
+        ragged = dict(lengths=wlen if min(wlen) < seq_len else None, window_ids=[sequence_offset + p for p in pairs])
+        if inject_steps:
+            st = torch.zeros(S, bk, seq_len, D, device=device)
+            for i, s in enumerate(ent["sequences"]):
+                st[:, i * n_smp:(i + 1) * n_smp, :ent["spans"][i][1]] = noise[s]["steps"][k].to(device).float()
+            eng.sample_loop_(curr_x, x_cond, S - 1, S, noise=st, prefix=pfx, **ragged)
+        else:
+            eng.sample_loop_(curr_x, x_cond, S - 1, S, noise_mode=_lib.NOISE_PHILOX, seed=model.philox_seed + k, prefix=pfx, **ragged)
+        model._note_job((bk, seq_len, S))
+        model._outlier_guard(eng, curr_x, x_cond)  # (may re-pack in another precision: take the engine afresh for the next window index)
+        eng = model.hip_engine()
+        aa, root, head = convert_model_res_to_data(ds, curr_x, recover, cur_jpos, parents)
+        o = 0
+        if k > 0:  # the one-sequence loop's stitching: move the window so that its frame OVERLAP - 1 meets the last stitched frame
+            move = head_last[idx] - head[:, OVERLAP - 1:OVERLAP, :]
+            root = root + move
+            head = head + move
+            o = OVERLAP
+        hi = min(t0 + seq_len, t_out)  # (frames past a short window's length land past its sequence's end: zeroed below)
+        whole_aa[idx, t0 + o:hi] = aa[:, o:hi - t0]
+        whole_root[idx, t0 + o:hi] = root[:, o:hi - t0]
+        head_last[idx] = head[:, seq_len - 1:seq_len, :]  # (read again only for pairs that continue: their window is full)
+        if any(cont):
+            sub = torch.as_tensor([i for i, c in enumerate(cont) if c], device=device)
+            aa_c, root_c = aa[sub].contiguous(), root[sub].contiguous()
+            nxt = _window_prefix_hip(ds, aa_c, root_c, OVERLAP, parents)
+            if nxt is None:
+                nxt = _window_prefix_torch(ds, aa_c, root_c, OVERLAP, parents)
+            prefix_all[idx[sub]] = nxt
+    out_lengths = torch.as_tensor([out_len[s] for s in range(n_seq) for _ in range(n_smp)], dtype=torch.int64)
+    keep = (torch.arange(t_out, device=device)[None, :] < out_lengths.to(device)[:, None]).float()
+    return whole_aa * keep[:, :, None, None], whole_root * keep[:, :, None], out_lengths
+
+
 # ------------------------------------------------------------------------------------------ checkpoints
 def build_stage2_model(window=120, d_model=512, n_head=4, n_dec_layers=4, d_k=256, d_v=256, repr_dim=22 * 3 + 22 * 6,
                        device=None):

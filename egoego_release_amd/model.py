@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from . import engine as engine_mod
 from .engine import HipEngine
 from . import plan as plan_mod
 from .precision import PrecisionProbe, _engine_cfg
@@ -482,10 +483,12 @@ class CondGaussianDiffusion(nn.Module):
                 _extract(self.posterior_log_variance_clipped, t, x_t.shape))
 
     @torch.no_grad()
-    def denoise(self, x, t, x_cond, padding_mask=None):
-        """denoise_fn(cat(x, x_cond), t) on the HIP path."""
+    def denoise(self, x, t, x_cond, padding_mask=None, lengths=None):
+        """denoise_fn(cat(x, x_cond), t) on the HIP path.  lengths [B]: window b attends over its first lengths[b] frames only (what
+        the reference computes on a window of that length); its rows past them are unspecified."""
         self._check_t(t)
-        return self.hip_engine(masked=padding_mask is not None).denoise(self._f32c(x), self._f32c(x_cond), t.long().contiguous(), padding_mask)
+        return self.hip_engine(masked=padding_mask is not None).denoise(self._f32c(x), self._f32c(x_cond), t.long().contiguous(), padding_mask,
+                                                                        lengths=lengths)
 
     def p_mean_variance(self, x, t, x_cond, clip_denoised, padding_mask=None):
         out = self.denoise(x, t, x_cond, padding_mask)
@@ -500,26 +503,32 @@ class CondGaussianDiffusion(nn.Module):
         return self.q_posterior(x_start=x_start, x_t=x, t=t)
 
     @torch.no_grad()
-    def p_sample(self, x, t, x_cond, clip_denoised=True, padding_mask=None, noise=None):
+    def p_sample(self, x, t, x_cond, clip_denoised=True, padding_mask=None, noise=None, lengths=None):
         """One ancestral step (fused on the GPU).  `noise=None` draws torch.randn_like(x), exactly
-        where the reference draws it."""
+        where the reference draws it.  lengths: as for denoise()."""
         eng = self.hip_engine(masked=padding_mask is not None)
         self._check_t(t)
         if noise is None:
             noise = torch.randn_like(x)
         out = self._f32c(x).clone()
-        eng.p_sample_(out, self._f32c(x_cond), t.long().contiguous(), self._f32c(noise), padding_mask, clip_denoised)
+        eng.p_sample_(out, self._f32c(x_cond), t.long().contiguous(), self._f32c(noise), padding_mask, clip_denoised, lengths=lengths)
         return out
 
     @torch.no_grad()
-    def p_sample_loop(self, shape, x_start, cond_mask, padding_mask=None, noise=None, prefix=None):
+    def p_sample_loop(self, shape, x_start, cond_mask, padding_mask=None, noise=None, prefix=None, lengths=None):
         """x_T ~ N(0,I); x_cond = x_start*(1-m) + m*N(0,I); then num_timesteps ancestral steps.
 
         noise (optional): dict with 'x_T' [B,T,D], 'cond' [B,T,D] and 'steps' [S,B,T,D] (step 0 = first
         executed, i.e. t = S-1) to inject the reference's own draws; otherwise torch's generator is
         consumed in the reference's order (sampling_rng='torch') or the per-step noise is drawn in-kernel
         (sampling_rng='philox').
+
+        lengths (optional, [B] host sequence or CUDA int tensor, each 1..T): a RAGGED batch — window b is sampled at its own length
+        (it attends over its time token and its first lengths[b] frames, like the reference called on a window of that length) and
+        its frames past it are returned as zeros.
         """
+        if lengths is not None:  # (bad host values raise here, before the draws and the measurement)
+            lengths = engine_mod.check_lengths(lengths, int(shape[0]), int(shape[1]), 0 if prefix is None else int(prefix.shape[1]))
         job = (int(shape[0]), int(shape[1]), int(self.num_timesteps))
         device = self.betas.device
         if device.type != "cuda":
@@ -542,19 +551,22 @@ class CondGaussianDiffusion(nn.Module):
             for s0 in range(0, S, chunk):
                 n = min(chunk, S - s0)
                 eng.sample_loop_(x, x_cond, S - 1 - s0, n, noise=self._f32c(steps[s0:s0 + n].to(device)), prefix=pfx,
-                                 row_mask=padding_mask)
+                                 row_mask=padding_mask, lengths=lengths)
         elif self.sampling_rng == "philox":
             eng.sample_loop_(x, x_cond, S - 1, S, noise_mode=_lib.NOISE_PHILOX, seed=self.philox_seed, prefix=pfx,
-                             row_mask=padding_mask)
+                             row_mask=padding_mask, lengths=lengths)
         elif self.sampling_rng == "torch":
-            self._torch_rng_chain(eng, x, x_cond, S, pfx, padding_mask)
+            self._torch_rng_chain(eng, x, x_cond, S, pfx, padding_mask, lengths)
         else:
             raise ValueError(f"unknown sampling_rng {self.sampling_rng}")
         self._note_job(job)
         self._outlier_guard(eng, x, x_cond)
+        if lengths is not None:  # frames past a window's length: computed (unspecified), returned as zeros
+            lt = torch.as_tensor(lengths).to(x.device)
+            x.mul_((torch.arange(x.shape[1], device=x.device)[None, :] < lt[:, None]).to(x.dtype)[:, :, None])
         return x
 
-    def _torch_rng_chain(self, eng, x, x_cond, S, prefix=None, padding_mask=None):
+    def _torch_rng_chain(self, eng, x, x_cond, S, prefix=None, padding_mask=None, lengths=None):
         """The S ancestral steps with torch's generator consumed exactly as the reference consumes it — one
         `randn_like(x)` per step, t = S-1 .. 0 (M:253, 267-268) — but drawn a chunk of steps ahead into one buffer
         that a single call of the HIP loop then walks: the draws are the same `normal_` launches on the same shape
@@ -571,13 +583,15 @@ class CondGaussianDiffusion(nn.Module):
             n = min(chunk, S - s0)
             for j in range(n):
                 buf[j].normal_()
-            eng.sample_loop_(x, x_cond, S - 1 - s0, n, noise=buf[:n], prefix=prefix, row_mask=padding_mask)
+            eng.sample_loop_(x, x_cond, S - 1 - s0, n, noise=buf[:n], prefix=prefix, row_mask=padding_mask, lengths=lengths)
 
     @torch.no_grad()
-    def sample(self, x_start, cond_mask, padding_mask=None, noise=None):
+    def sample(self, x_start, cond_mask, padding_mask=None, noise=None, lengths=None):
         # like the reference (M:528-535): padding_mask is accepted and ignored; eval() then train()
+        # lengths [B]: every window is sampled at its own length, frames past it come back as zeros (p_sample_loop) — the windows
+        # of motion_data.build_motion_windows feed sample(motion, mask, lengths=windows.seq_len) directly
         self.denoise_fn.eval()
-        res = self.p_sample_loop(x_start.shape, x_start, cond_mask, noise=noise)
+        res = self.p_sample_loop(x_start.shape, x_start, cond_mask, noise=noise, lengths=lengths)
         self.denoise_fn.train()
         return res
 

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*) and the motion windows (egoego_win_*) were added under 8: purely additive, no existing entry changed */
+#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*), the motion windows (egoego_win_*) and the ragged sampling entry points (egoego_*_ragged) were added under 8: purely additive, no existing entry changed */
 
 enum {
     EGOEGO_OK = 0,
@@ -182,6 +182,38 @@ int egoego_sample_loop(egoego_ctx* ctx, float* d_x, const float* d_x_cond, int t
                        const float* d_prefix, int prefix_len, const float* d_row_mask, int B, int T,
                        void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* RAGGED batches: windows of different lengths in one call.  The three entry points below are egoego_denoise, egoego_p_sample
+ * and egoego_sample_loop with two more arguments (the ABI version stays 8: purely additive):
+ *   d_lengths     int32 DEVICE array [B], each 1..T: the frames of window b.  Window b then attends over its time token and its
+ *                 first d_lengths[b] frames only — what the reference computes when it calls the denoiser on a window of that
+ *                 length (M:355-356) — where a padding mask (d_row_mask: still available, and independent) only zeroes sublayer
+ *                 outputs while the padded frames keep acting as keys (TM:135,139).  NULL: every window has T frames.
+ *   d_window_ids  int64 DEVICE array [B]: window b draws the Philox stream of id d_window_ids[b], so a compacted or reordered set
+ *                 of windows keeps each window's own noise.  NULL: window_offset + b.
+ * The values are the caller's responsibility (the Python layer validates them, and that prefix_len <= min(lengths)); both arrays
+ * must stay valid until the call's work on `stream` is done.
+ * What a ragged call guarantees: the rows of a window up to its length depend on that window's own rows and its own length only —
+ * they are bit-identical with the window alone in the batch, at any position of it, among any other lengths and for any ids of
+ * the other windows; with every length equal to T (and ids window_offset + b) they are the bits of the uniform entry point.  The
+ * rows PAST a window's length are unspecified but finite: they are computed like any others (no row mask is implied), attend over
+ * the window's valid keys and stay inside the per-step clamp; the outlier monitor records them as computed.  Tile and form
+ * selection is that of the padded (B, T): a short window costs what a full one does.
+ * One captured step serves every ragged call of a shape on a workspace (the arrays are step state, never graph arguments); uniform
+ * and ragged calls of the same shape keep separate graphs (they launch different kernel instantiations).
+ * NOT ragged: egoego_ddim_loop and egoego_debug_stage take one T for the whole batch. */
+int egoego_denoise_ragged(egoego_ctx* ctx, const float* d_x, const float* d_x_cond, const int64_t* d_t,
+                          const float* d_row_mask, const int32_t* d_lengths, float* d_out, int B, int T,
+                          void* d_workspace, size_t workspace_bytes, void* stream);
+int egoego_p_sample_ragged(egoego_ctx* ctx, float* d_x, const float* d_x_cond, const int64_t* d_t,
+                           const float* d_row_mask, const int32_t* d_lengths, const int64_t* d_window_ids,
+                           const float* d_noise, int noise_mode, uint64_t seed, int64_t window_offset, int clip_denoised,
+                           int B, int T, void* d_workspace, size_t workspace_bytes, void* stream);
+int egoego_sample_loop_ragged(egoego_ctx* ctx, float* d_x, const float* d_x_cond, int t_start, int n_steps,
+                              const float* d_noise, int noise_mode, uint64_t seed, int64_t window_offset,
+                              const float* d_prefix, int prefix_len, const float* d_row_mask,
+                              const int32_t* d_lengths, const int64_t* d_window_ids, int B, int T,
+                              void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* DDIM sampler (Song et al. 2021) on a strided subsequence of timesteps.  NOT in the reference —
  * no oracle from the reference exists for it.  timesteps_host: HOST int32 array of n strictly descending timesteps.
  * eta in [0, 1]: 0 = deterministic; 1 on the FULL timestep list is the ancestral DDPM chain of egoego_sample_loop
@@ -244,7 +276,9 @@ const char* egoego_last_kernel_name(const egoego_ctx* ctx, int kernel_id);
  *   precision 9 at T + 1 >= 65, with EGOEGO_FLAG_FC24 or not: both LayerNorms of every layer;
  *   precisions 3 / 1, and layers >= 8: nothing.
  * Every row of the B windows is recorded: with a row mask each window's padding rows (T + 1 .. Lr - 1) are zero, without one they
- * are recorded as computed.  Only the rows that pad the call to whole token blocks are not.  Weights packed from a mean-shifted
+ * are recorded as computed.  A ragged call (egoego_*_ragged) implies no row mask: the rows past a window's own length are computed
+ * like any others — over the window's valid keys only, so finite and inside the per-step clamp — and recorded as computed.
+ * Only the rows that pad the call to whole token blocks are not.  Weights packed from a mean-shifted
  * state dict record the shifted rows (the LayerNorm output minus the per-feature shift).
  * host_out[2 * layer + k] (k = 0: self_attn.layer_norm, k = 1: pos_ffn.layer_norm; n_out <= 16 entries, 0 = nothing recorded)
  * receives the maxima accumulated by every call on this workspace since the last reset; reset != 0 clears them afterwards.

@@ -14,7 +14,10 @@ of this repo: every asset is an input file, and without `--w
 
   --head_pose     .npy [T,7] or [B,T,7]: xyz + quaternion (w,x,y,z), what trainer.full_body_gen_cond_head_pose_sliding_window
                   takes (trainer_amass_cond_motion_diffusion.py:261-276); or the reference's demo pickle
-                  (test_data/ares/demo_ares_data.p: its 'head_qpos')
+                  (test_data/ares/demo_ares_data.p: its 'head_qpos').  SEVERAL files (trajectories of any lengths, each [T,7]):
+                  they are sampled together through the ragged sliding-window call
+                  (harness.full_body_gen_cond_head_pose_sliding_window_ragged: one batch per window index over all of them, in-kernel
+                  Philox noise); the outputs are then padded to the longest result, with "out_lengths" giving each one's frames
   --stats         the dataset's min/max statistics pickle (global_jpos_min / global_jpos_max, amass_diffusion_dataset.py:232-239;
                   tools/build_motion_windows.py writes it from the raw motion)
   --rest_offsets  .npy [22,3] rest-pose joint offsets (AMASSDataset.rest_human_offsets; tools/build_motion_windows.py writes it
@@ -83,7 +86,7 @@ def parse_opt(argv=None):
     p.add_argument("--use_min_max", action="store_true", help="accepted for flag compatibility (always on in the shipped configs)")
     p.add_argument("--canonicalize_init_head", action="store_true", help="accepted for flag compatibility (always on)")
     # assets
-    p.add_argument("--head_pose", required=True)
+    p.add_argument("--head_pose", required=True, nargs="+", help="one trajectory file, or several (sampled together, ragged)")
     p.add_argument("--stats", required=True)
     p.add_argument("--rest_offsets", required=True)
     p.add_argument("--parents", default="", help="comma-separated 22 parent indices (default: SMPL-H kintree)")
@@ -127,6 +130,11 @@ def self_launch(n, argv):
 
 def main(argv=None):
     opt = parse_opt(argv)
+    several = len(opt.head_pose) > 1
+    if several and (opt.gpus >= 1 or opt.gt_jpos or opt.noise):
+        raise SystemExit("several --head_pose files run the single-process ragged call: --gpus, --gt_jpos and --noise take one trajectory")
+    if not several:
+        opt.head_pose = opt.head_pose[0]
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(opt.gpus, sys.argv[1:] if argv is None else argv)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -173,6 +181,17 @@ def main(argv=None):
         head_pose = load_head_pose(opt.head_pose)
         aa, root = D.harness_sharded(model, ds, head_pose, sample_bs=opt.diffusion_batch_size, seed=opt.seed, parents=parents)
         head_pose = head_pose.repeat_interleave(opt.diffusion_batch_size, 0)
+    elif several:
+        # trajectories of different lengths: every window index runs once for all of them (the per-step draws are in-kernel Philox)
+        poses = []
+        for path in opt.head_pose:
+            hp = load_head_pose(path)
+            if hp.shape[0] != 1:
+                raise SystemExit(f"{path}: one [T,7] trajectory per file expected when several files are given, got {tuple(hp.shape)}")
+            poses.append(hp[0].to(dev))
+        model.sampling_rng = "philox"
+        aa, root, out_lengths = harness.full_body_gen_cond_head_pose_sliding_window_ragged(model, ds, poses,
+                                                                                           samples_per_sequence=opt.diffusion_batch_size)
     else:
         head_pose = load_head_pose(opt.head_pose).repeat_interleave(opt.diffusion_batch_size, 0).to(dev)
         noise = torch.load(opt.noise, map_location="cpu") if opt.noise else None
@@ -189,6 +208,17 @@ def main(argv=None):
     gq, gj = ds.fk_smpl(root.reshape(-1, 3), aa.reshape(-1, 22, 3))
     gj = gj.reshape(b, t, 22, 3)
     out = {"local_aa": aa.cpu().numpy(), "root_trans": root.cpu().numpy(), "global_jpos": gj.cpu().numpy()}
+    if several:
+        keep = (torch.arange(t)[None, :] < out_lengths[:, None]).numpy()
+        out["global_jpos"] = out["global_jpos"] * keep[:, :, None, None]  # (FK of the zero rows past a result's end is not a pose)
+        out["out_lengths"] = out_lengths.numpy()
+        rep = {"frames": [int(v) for v in out_lengths], "samples": int(b), "sequences": len(poses),
+               "windows": sum(len(harness.window_spans(int(p.shape[0]), opt.diffusion_window)) for p in poses) * opt.diffusion_batch_size,
+               "diffusion_steps": opt.timesteps, "seconds": round(el, 3), "checkpoint": info, "ranks": world, "sharding": None,
+               "ragged": True}
+        np.savez_compressed(opt.out, **out)
+        print(json.dumps(rep), flush=True)
+        return rep
     rep = {"frames": int(t), "samples": int(b), "windows": len(range(0, head_pose.shape[1], opt.diffusion_window - harness.OVERLAP)),
            "diffusion_steps": opt.timesteps, "seconds": round(el, 3), "checkpoint": info, "ranks": world,
            "sharding": "by sequence (dist.harness_sharded)" if opt.gpus >= 1 else None}
