@@ -77,7 +77,7 @@ class BodyModelDesc(C.Structure):
 EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoego_ctx_destroy",
            "egoego_load_weights", "egoego_load_schedule", "egoego_workspace_bytes", "egoego_denoise",
            "egoego_p_sample", "egoego_sample_loop", "egoego_denoise_ragged", "egoego_p_sample_ragged", "egoego_sample_loop_ragged",
-           "egoego_ddim_loop", "egoego_rot6d_to_matrix", "egoego_convert_model_res", "egoego_window_prefix", "egoego_window_condition",
+           "egoego_ddim_loop", "egoego_ddim_loop_ragged", "egoego_rot6d_to_matrix", "egoego_convert_model_res", "egoego_window_prefix", "egoego_window_condition",
            "egoego_profile_begin", "egoego_profile_end", "egoego_debug_stage", "egoego_last_kernel_name", "egoego_outlier_stats",
            "egoego_s1_last_error", "egoego_s1_ctx_create", "egoego_s1_ctx_destroy", "egoego_s1_load_weights",
            "egoego_s1_workspace_bytes", "egoego_s1_encode", "egoego_s1_gravity_features", "egoego_s1_integrate",
@@ -139,6 +139,9 @@ def load():
     lib.egoego_p_sample_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, u64, i64, i32, i32, i32, vp, sz, vp]
     lib.egoego_sample_loop_ragged.argtypes = [vp, vp, vp, i32, i32, vp, i32, u64, i64, vp, i32, vp, vp, vp, i32, i32, vp, sz, vp]
     lib.egoego_ddim_loop.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), i32, C.c_float, vp, i32, u64, i64, i32, i32, vp, sz, vp]
+    # + d_prefix, prefix_len, d_row_mask, d_lengths, d_window_ids behind window_offset, as egoego_sample_loop_ragged orders them
+    lib.egoego_ddim_loop_ragged.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), i32, C.c_float, vp, i32, u64, i64, vp, i32, vp, vp, vp,
+                                            i32, i32, vp, sz, vp]
     lib.egoego_rot6d_to_matrix.argtypes = [vp, vp, i64, vp]
     lib.egoego_convert_model_res.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int32), i32, i32, i32, vp, vp, vp, vp]
     lib.egoego_window_condition.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]

@@ -1591,6 +1591,75 @@ static int sample_loop_impl(egoego_ctx* c, float* d_x, const float* d_xc, int t_
     return run_steps(c, g, w, io, key, call, n_steps, s);
 }
 
+// The strided sampler behind egoego_ddim_loop (every added argument nullptr / 0: the launches and the graph key it always had) and
+// egoego_ddim_loop_ragged.  The prefix, the row mask, the lengths and the ids reach the step exactly as in sample_loop_impl.
+static int ddim_loop_impl(egoego_ctx* c, float* d_x, const float* d_xc, const int32_t* ts, int n, float eta, const float* d_noise,
+                          int noise_mode, uint64_t seed, int64_t window_offset, const float* d_prefix, int prefix_len,
+                          const float* d_row_mask, const int32_t* d_lengths, const int64_t* d_window_ids, int B, int T, void* d_ws,
+                          size_t ws_bytes, void* stream) {
+    if (int r = check_ready(c, true)) return r;
+    if (!d_x || !d_xc || !ts || n < 1 || n > c->S) return fail(EGOEGO_E_INVALID, "bad argument");
+    if (!(eta >= 0.f && eta <= 1.f)) return fail(EGOEGO_E_INVALID, "eta must be in [0, 1], got %g", (double)eta);
+    if (noise_mode < 0 || noise_mode > 2) return fail(EGOEGO_E_INVALID, "unknown noise_mode %d", noise_mode);
+    if (noise_mode == EGOEGO_NOISE_INJECTED && !d_noise) return fail(EGOEGO_E_INVALID, "noise_mode INJECTED needs d_noise");
+    if (eta > 0.f && noise_mode == EGOEGO_NOISE_NONE) return fail(EGOEGO_E_INVALID, "eta > 0 needs a noise source (INJECTED or PHILOX)");
+    for (int i = 0; i < n; ++i)
+        if (ts[i] < 0 || ts[i] >= c->S || (i && ts[i] >= ts[i - 1]))
+            return fail(EGOEGO_E_INVALID, "DDIM timesteps must be strictly descending in [0, %d)", c->S);
+    if (d_prefix && (prefix_len < 1 || prefix_len > T)) return fail(EGOEGO_E_INVALID, "bad prefix_len %d", prefix_len);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(c->device));
+    Geometry g;
+    Workspace w;
+    if (int r = prepare(c, B, T, d_ws, ws_bytes, g, w)) return r;
+    StepIO io{};
+    if (int r = pack_inputs(c, g, w, d_x, d_xc, d_row_mask, &io.row_mask, s)) return r;
+    // The timestep list and each step's coefficients (Song et al. 2021, eq. 12 / 16), read by the step kernels through
+    // the step index:  sig = eta sqrt((1 - abar_prev) / (1 - abar_t)) sqrt(1 - abar_t / abar_prev),
+    // x <- sqrt(abar_prev) x0 + sqrt(1 - abar_prev - sig^2) eps + sig z;  abar_prev = 1 after the last entry.
+    // Staged in a pinned slot that is only reused once the copy that read it has finished: no stream synchronisation.
+    {
+        const int slot = c->stage_next;
+        c->stage_next = (slot + 1) % egoego_ctx::N_STAGE;
+        const size_t bytes = (size_t)c->S * (sizeof(int) + 4 * sizeof(float));
+        if (!c->stage[slot]) {
+            HIP_TRY(hipHostMalloc(&c->stage[slot], bytes, hipHostMallocDefault));
+            HIP_TRY(hipEventCreateWithFlags(&c->stage_ev[slot], hipEventDisableTiming));
+        } else {
+            HIP_TRY(hipEventSynchronize(c->stage_ev[slot]));
+        }
+        int* h_ts = (int*)c->stage[slot];
+        float* h_tab = (float*)(h_ts + c->S);
+        for (int i = 0; i < n; ++i) {
+            const double at = c->abar_host[ts[i]], ap = (i + 1 < n) ? (double)c->abar_host[ts[i + 1]] : 1.0;
+            double sig = 0.0;
+            if (eta > 0.f && ap < 1.0 && at < 1.0) sig = (double)eta * sqrt((1.0 - ap) / (1.0 - at)) * sqrt(fmax(1.0 - at / ap, 0.0));
+            h_ts[i] = ts[i];
+            h_tab[4 * i + 0] = (float)sqrt(ap);
+            h_tab[4 * i + 1] = (float)sqrt(fmax(1.0 - ap - sig * sig, 0.0));
+            h_tab[4 * i + 2] = (float)sig;
+            h_tab[4 * i + 3] = 0.f;
+        }
+        HIP_TRY(hipMemcpyAsync(w.step_ts, h_ts, sizeof(int) * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.step_tab, h_tab, sizeof(float) * 4 * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(c->stage_ev[slot], s));
+    }
+    io.stop_layer = io.stop_stage = -1;
+    io.run_out = true;
+    base_out_params(c, g, w, io.out);
+    io.out.mode = 2;
+    io.out.noise_mode = eta > 0.f ? noise_mode : EGOEGO_NOISE_NONE;
+    io.out.ddim_tab = w.step_tab;
+    io.out.step_elems = (size_t)B * T * c->D;
+    io.out.prefix_len = d_prefix ? prefix_len : 0;
+    // as in sample_loop_impl: the arrays are step state, arrays against none selects other kernel instantiations
+    io.ragged = d_lengths != nullptr || d_window_ids != nullptr;
+    const StepKey key{B, T, 2, io.out.noise_mode, io.out.prefix_len, 1, 1, d_row_mask ? 1 : 0, io.ragged ? 1 : 0, d_ws};
+    const StepCall call{0, d_x, io.out.noise_mode == EGOEGO_NOISE_INJECTED ? d_noise : nullptr, d_prefix, seed, window_offset, d_lengths,
+                        d_window_ids};
+    return run_steps(c, g, w, io, key, call, n, s);
+}
+
 extern "C" {
 
 int egoego_denoise(egoego_ctx* c, const float* d_x, const float* d_xc, const int64_t* d_t, const float* d_row_mask,
@@ -1631,62 +1700,15 @@ int egoego_sample_loop_ragged(egoego_ctx* c, float* d_x, const float* d_xc, int 
 
 int egoego_ddim_loop(egoego_ctx* c, float* d_x, const float* d_xc, const int32_t* ts, int n, float eta, const float* d_noise,
                      int noise_mode, uint64_t seed, int64_t window_offset, int B, int T, void* d_ws, size_t ws_bytes, void* stream) {
-    if (int r = check_ready(c, true)) return r;
-    if (!d_x || !d_xc || !ts || n < 1 || n > c->S) return fail(EGOEGO_E_INVALID, "bad argument");
-    if (!(eta >= 0.f && eta <= 1.f)) return fail(EGOEGO_E_INVALID, "eta must be in [0, 1], got %g", (double)eta);
-    if (noise_mode < 0 || noise_mode > 2) return fail(EGOEGO_E_INVALID, "unknown noise_mode %d", noise_mode);
-    if (noise_mode == EGOEGO_NOISE_INJECTED && !d_noise) return fail(EGOEGO_E_INVALID, "noise_mode INJECTED needs d_noise");
-    if (eta > 0.f && noise_mode == EGOEGO_NOISE_NONE) return fail(EGOEGO_E_INVALID, "eta > 0 needs a noise source (INJECTED or PHILOX)");
-    for (int i = 0; i < n; ++i)
-        if (ts[i] < 0 || ts[i] >= c->S || (i && ts[i] >= ts[i - 1]))
-            return fail(EGOEGO_E_INVALID, "DDIM timesteps must be strictly descending in [0, %d)", c->S);
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(c->device));
-    Geometry g;
-    Workspace w;
-    if (int r = prepare(c, B, T, d_ws, ws_bytes, g, w)) return r;
-    StepIO io{};
-    if (int r = pack_inputs(c, g, w, d_x, d_xc, nullptr, &io.row_mask, s)) return r;
-    // The timestep list and each step's coefficients (Song et al. 2021, eq. 12 / 16), read by the step kernels through
-    // the step index:  sig = eta sqrt((1 - abar_prev) / (1 - abar_t)) sqrt(1 - abar_t / abar_prev),
-    // x <- sqrt(abar_prev) x0 + sqrt(1 - abar_prev - sig^2) eps + sig z;  abar_prev = 1 after the last entry.
-    // Staged in a pinned slot that is only reused once the copy that read it has finished: no stream synchronisation.
-    {
-        const int slot = c->stage_next;
-        c->stage_next = (slot + 1) % egoego_ctx::N_STAGE;
-        const size_t bytes = (size_t)c->S * (sizeof(int) + 4 * sizeof(float));
-        if (!c->stage[slot]) {
-            HIP_TRY(hipHostMalloc(&c->stage[slot], bytes, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&c->stage_ev[slot], hipEventDisableTiming));
-        } else {
-            HIP_TRY(hipEventSynchronize(c->stage_ev[slot]));
-        }
-        int* h_ts = (int*)c->stage[slot];
-        float* h_tab = (float*)(h_ts + c->S);
-        for (int i = 0; i < n; ++i) {
-            const double at = c->abar_host[ts[i]], ap = (i + 1 < n) ? (double)c->abar_host[ts[i + 1]] : 1.0;
-            double sig = 0.0;
-            if (eta > 0.f && ap < 1.0 && at < 1.0) sig = (double)eta * sqrt((1.0 - ap) / (1.0 - at)) * sqrt(fmax(1.0 - at / ap, 0.0));
-            h_ts[i] = ts[i];
-            h_tab[4 * i + 0] = (float)sqrt(ap);
-            h_tab[4 * i + 1] = (float)sqrt(fmax(1.0 - ap - sig * sig, 0.0));
-            h_tab[4 * i + 2] = (float)sig;
-            h_tab[4 * i + 3] = 0.f;
-        }
-        HIP_TRY(hipMemcpyAsync(w.step_ts, h_ts, sizeof(int) * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w.step_tab, h_tab, sizeof(float) * 4 * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(c->stage_ev[slot], s));
-    }
-    io.stop_layer = io.stop_stage = -1;
-    io.run_out = true;
-    base_out_params(c, g, w, io.out);
-    io.out.mode = 2;
-    io.out.noise_mode = eta > 0.f ? noise_mode : EGOEGO_NOISE_NONE;
-    io.out.ddim_tab = w.step_tab;
-    io.out.step_elems = (size_t)B * T * c->D;
-    const StepKey key{B, T, 2, io.out.noise_mode, 0, 1, 1, 0, 0, d_ws};
-    const StepCall call{0, d_x, io.out.noise_mode == EGOEGO_NOISE_INJECTED ? d_noise : nullptr, nullptr, seed, window_offset, nullptr, nullptr};
-    return run_steps(c, g, w, io, key, call, n, s);
+    return ddim_loop_impl(c, d_x, d_xc, ts, n, eta, d_noise, noise_mode, seed, window_offset, nullptr, 0, nullptr, nullptr, nullptr, B, T,
+                          d_ws, ws_bytes, stream);
+}
+int egoego_ddim_loop_ragged(egoego_ctx* c, float* d_x, const float* d_xc, const int32_t* ts, int n, float eta, const float* d_noise,
+                            int noise_mode, uint64_t seed, int64_t window_offset, const float* d_prefix, int prefix_len,
+                            const float* d_row_mask, const int32_t* d_lengths, const int64_t* d_window_ids, int B, int T, void* d_ws,
+                            size_t ws_bytes, void* stream) {
+    return ddim_loop_impl(c, d_x, d_xc, ts, n, eta, d_noise, noise_mode, seed, window_offset, d_prefix, prefix_len, d_row_mask,
+                          d_lengths, d_window_ids, B, T, d_ws, ws_bytes, stream);
 }
 
 int egoego_rot6d_to_matrix(const float* d_in, float* d_out, int64_t n, void* stream) {

@@ -131,7 +131,8 @@ def harness_noise(n_pairs, n_frames, seq_len, seed=0, d_feats=198):
     return {"x_all": x_all, "cond": cond}
 
 
-def harness_sharded(model, ds, head_pose, sample_bs=1, seed=0, parents=None, group=None, force_collective=False, harness_fn=None):
+def harness_sharded(model, ds, head_pose, sample_bs=1, seed=0, parents=None, group=None, force_collective=False, harness_fn=None,
+                    sampler="ddpm", n_steps=50, eta=0.0):
     """`Trainer.full_body_gen_cond_head_pose_sliding_window` (trainer_amass_cond_motion_diffusion.py:261-276) over the GPUs of a
     node, sharded by SEQUENCE: head_pose [Bseq, T, 7] (every rank holds all of it: it is small) holds Bseq
     head trajectories, each sampled `sample_bs` times (run_egoego.py:146-148 repeats a sequence's head pose sample_bs times).
@@ -143,8 +144,11 @@ def harness_sharded(model, ds, head_pose, sample_bs=1, seed=0, parents=None, gro
     `philox_seed` is set from it for the call), so two calls with different seeds share no noise.
     All ranks sample from one plan and the runtime guard's verdict is collective (plan.py; a rank without pairs joins in).
     Returns (local axis-angle [Bseq * sample_bs, T', 22, 3], root [Bseq * sample_bs, T', 3]) on every rank.
-    harness_fn(head_pose_slice, noise_slice, pair_offset) -> (aa, root): stand-in for tests; default = the HIP harness."""
+    harness_fn(head_pose_slice, noise_slice, pair_offset) -> (aa, root): stand-in for tests; default = the HIP harness.
+    sampler / n_steps / eta: handed to the harness (sampler="ddim": the strided sampler per window; eta > 0 needs
+    model.sampling_rng = "philox")."""
     from . import harness
+    harness.sampler_timesteps(model, sampler, n_steps, eta, False)  # (raises on every rank alike, before any collective)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     pairs = head_pose.repeat_interleave(sample_bs, dim=0)
@@ -162,7 +166,8 @@ def harness_sharded(model, ds, head_pose, sample_bs=1, seed=0, parents=None, gro
             model.philox_seed = int(seed) * 1000003 + 11  # (+ the window index inside the harness)
             try:
                 return harness.full_body_gen_cond_head_pose_sliding_window(model, ds, hp.to(dev), noise=nz, parents=parents,
-                                                                           window_offset=off, group=grp, global_pairs=n)
+                                                                           window_offset=off, group=grp, global_pairs=n,
+                                                                           sampler=sampler, n_steps=n_steps, eta=eta)
             finally:
                 model.philox_seed = keep
     t_out = harness.output_frames(n_frames, seq_len)

@@ -257,14 +257,28 @@ class HipEngine:
                                                self._stream()))
         return x
 
-    def ddim_loop_(self, x, x_cond, timesteps, eta=0.0, noise=None, noise_mode=None, seed=0, window_offset=0):
-        """In-place DDIM over the descending `timesteps`; eta > 0 adds eta-weighted noise (injected [n, B, T, D] or Philox)."""
+    def ddim_loop_(self, x, x_cond, timesteps, eta=0.0, noise=None, noise_mode=None, seed=0, window_offset=0,
+                   prefix=None, row_mask=None, lengths=None, window_ids=None):
+        """In-place DDIM over the descending `timesteps`; eta > 0 adds eta-weighted noise (injected [n, B, T, D] or Philox).
+        prefix / row_mask / lengths / window_ids as for sample_loop_: the prefix is re-imposed after every step."""
         B, T, D = x.shape
+        lt, it = self._ragged(lengths, window_ids, B, T, prefix.shape[1] if prefix is not None else 0)
         ws, n = self.workspace(B, T)
         arr = (C.c_int32 * len(timesteps))(*[int(v) for v in timesteps])
         if noise_mode is None:
             noise_mode = _lib.NOISE_INJECTED if noise is not None else (_lib.NOISE_PHILOX if eta > 0 else _lib.NOISE_NONE)
         npnt = self._chk(noise, (len(timesteps), B, T, D)) if noise is not None else None
+        pp, plen = None, 0
+        if prefix is not None:
+            plen = prefix.shape[1]
+            pp = self._chk(prefix, (B, plen, D))
+        m, mp = self._mask(row_mask, B, T)
+        if pp is not None or mp is not None or lt is not None or it is not None:
+            _lib.check(self.lib.egoego_ddim_loop_ragged(self._ctx, self._chk(x), self._chk(x_cond, x.shape), arr, len(timesteps),
+                                                        float(eta), npnt, noise_mode, seed, window_offset, pp, plen, mp,
+                                                        lt.data_ptr() if lt is not None else None,
+                                                        it.data_ptr() if it is not None else None, B, T, ws, n, self._stream()))
+            return x
         _lib.check(self.lib.egoego_ddim_loop(self._ctx, self._chk(x), self._chk(x_cond, x.shape), arr, len(timesteps),
                                              float(eta), npnt, noise_mode, seed, window_offset, B, T, ws, n, self._stream()))
         return x

@@ -276,9 +276,33 @@ def output_frames(num_frames, seq_len):
     return sum(n for _, n in spans) - OVERLAP * max(0, len(spans) - 1)
 
 
+SAMPLERS = ("ddpm", "ddim")
+
+
+def sampler_timesteps(model, sampler, n_steps, eta, inject_steps):
+    """What the `sampler` / `n_steps` / `eta` arguments of the sliding-window calls select, checked on the host before anything runs:
+    None for "ddpm" (the reference's ancestral chain over every timestep), the descending list model.ddim_timesteps(n_steps) for
+    "ddim" (the strided sampler, not in the reference: DESIGN.md 5b-3).  eta == 0 draws nothing per step and works under any
+    sampling_rng; eta > 0 without injected steps draws in-kernel Philox noise, so it needs sampling_rng = "philox" — there is no
+    reference draw order to reproduce."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}: one of {SAMPLERS} expected")
+    if sampler == "ddpm":
+        return None
+    if int(n_steps) < 1:
+        raise ValueError(f"n_steps must be positive, got {n_steps}")
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must be in [0, 1], got {eta}")
+    if eta > 0 and not inject_steps and model.sampling_rng != "philox":
+        raise ValueError(f'sampler="ddim" with eta > 0 draws its per-step noise in-kernel: set model.sampling_rng = "philox" '
+                         f'(it is "{model.sampling_rng}") or inject noise[\'steps\']')
+    return model.ddim_timesteps(int(n_steps))
+
+
 @torch.no_grad()
 def p_sample_loop_sliding_window_w_canonical(model, ds, shape, global_head_jpos, global_head_jquat, cond_mask,
-                                             noise=None, parents=None, window_offset=0, group=None, global_pairs=None):
+                                             noise=None, parents=None, window_offset=0, group=None, global_pairs=None,
+                                             sampler="ddpm", n_steps=50, eta=0.0):
     """M:329-467.  Windows of `model.seq_len` frames, stride seq_len-10; window k+1 is conditioned on the
     last 10 frames of window k, re-canonicalised, by overwriting its first 10 frames after every step.
 
@@ -289,9 +313,15 @@ def p_sample_loop_sliding_window_w_canonical(model, ds, shape, global_head_jpos,
     collective then); a rank without sequences (b = 0) walks the same collective calls and returns empty tensors.
     global_pairs (dist.harness_sharded): the (sequence, sample) pairs of the WHOLE call over all ranks — the plan's small-job rule is
     sized by the global job, so that the precision picked does not depend on how many ranks share it.
+    sampler="ddim": every window runs the strided sampler (engine.ddim_loop_) over model.ddim_timesteps(n_steps) at `eta` instead of
+    the ancestral chain, with the same prefix in-painting after every step and the seed philox_seed + window index; injected
+    noise['steps'][k] is then [len(timesteps), B, Tw, D] and read at eta > 0 only (sampler_timesteps has the rules).
+    A short last window runs padded to seq_len at its own length (engine `lengths=`), as in the ragged harness: the two harnesses
+    then agree bit for bit.
     """
+    ts = sampler_timesteps(model, sampler, n_steps, eta, noise is not None and "steps" in noise)
     b = shape[0]
-    S = model.num_timesteps
+    S = model.num_timesteps if ts is None else len(ts)  # steps per window: what the plan's small-job rule is sized by
     seq_len = model.seq_len
     stride = seq_len - OVERLAP
     spans = window_spans(global_head_jpos.shape[1], seq_len)
@@ -320,18 +350,40 @@ def p_sample_loop_sliding_window_w_canonical(model, ds, shape, global_head_jpos,
             break
         cur_quat = jquat_all[:, t_idx:t_idx + seq_len]
         cur_jpos = jpos_all[:, t_idx:t_idx + seq_len]
+        cm = cond_mask[:, t_idx:t_idx + seq_len].to(device)
+        n_real = curr_x.shape[1]
+        # The strided sampler runs a short (last) window the way the ragged harness does: padded to seq_len (x_T and the noise by zeros,
+        # head pose and mask by their last frame) and sampled at its own length through `lengths`.  Its real frames are then the
+        # ragged call's bits, so both harnesses give ONE result in every precision; and a 50-step chain does not pay a second
+        # workspace, first-step launch and graph capture for a shape it meets once.  (The ancestral chain keeps the reference's
+        # form: the window at its own T.)
+        padded = ts is not None and n_real < seq_len
+        if padded:
+            grow = lambda v, last: torch.cat((v, (v[:, -1:] if last else v.new_zeros(v.shape[0], 1, v.shape[2])).expand(-1, seq_len - n_real, -1)), dim=1).contiguous()
+            curr_x, cur_quat, cur_jpos, cm = grow(curr_x, False), grow(cur_quat, True), grow(cur_jpos, True), grow(cm, True)
         cond = _window_condition_hip(ds, cur_jpos, cur_quat)
         if cond is not None:
             x_start, recover = cond
         else:
             x_start, recover = _window_condition_torch(ds, cur_jpos, cur_quat)
-        cm = cond_mask[:, t_idx:t_idx + seq_len].to(device)
-        cn = noise["cond"][w_idx].to(device) if noise is not None else torch.randn_like(x_start)
+        if padded:
+            cn = grow(noise["cond"][w_idx].to(device).float() if noise is not None else torch.randn_like(x_start[:, :n_real]), False)
+        else:
+            cn = noise["cond"][w_idx].to(device) if noise is not None else torch.randn_like(x_start)
         x_cond = (x_start * (1.0 - cm) + cm * cn).float().contiguous()
         pfx = prefix if t_idx > 0 else None
         if t_idx == 0:  # (the first window's conditions shape stage 2 of the plan's measurement; collective like the call above)
             eng = model.hip_engine(verify=True, job=job, group=group, conditions=x_cond)
-        if noise is not None and "steps" in noise:
+        if ts is not None:
+            own = dict(lengths=[n_real] * b) if padded else {}
+            if eta > 0 and noise is not None and "steps" in noise:
+                st = noise["steps"][w_idx].to(device).float()
+                if padded:
+                    st = torch.cat((st, st.new_zeros(st.shape[0], b, seq_len - n_real, st.shape[3])), dim=2)
+                eng.ddim_loop_(curr_x, x_cond, ts, eta=eta, noise=st.contiguous(), prefix=pfx, **own)
+            else:
+                eng.ddim_loop_(curr_x, x_cond, ts, eta=eta, seed=model.philox_seed + w_idx, window_offset=window_offset, prefix=pfx, **own)
+        elif noise is not None and "steps" in noise:
             eng.sample_loop_(curr_x, x_cond, S - 1, S, noise=noise["steps"][w_idx].to(device).float().contiguous(), prefix=pfx)
         elif model.sampling_rng == "philox" or noise is not None:
             eng.sample_loop_(curr_x, x_cond, S - 1, S, noise_mode=_lib.NOISE_PHILOX, seed=model.philox_seed + w_idx,
@@ -342,6 +394,8 @@ def p_sample_loop_sliding_window_w_canonical(model, ds, shape, global_head_jpos,
         model._outlier_guard(eng, curr_x, x_cond, group=group)  # (may re-pack in another precision — on every rank of the group alike —: take the engine afresh for the next window)
         eng = model.hip_engine()
         aa, root, head = convert_model_res_to_data(ds, curr_x, recover, cur_jpos, parents)
+        if padded:  # (what the sampler left in the padded frames is never read)
+            aa, root, head = aa[:, :n_real], root[:, :n_real], head[:, :n_real]
         if t_idx == 0:
             whole_aa, whole_root, whole_head = aa, root, head
         else:
@@ -364,22 +418,27 @@ def p_sample_loop_sliding_window_w_canonical(model, ds, shape, global_head_jpos,
 
 @torch.no_grad()
 def sample_sliding_window_w_canonical(model, ds, global_head_jpos, global_head_jquat, x_start, cond_mask, noise=None,
-                                      parents=None, window_offset=0, group=None, global_pairs=None):
+                                      parents=None, window_offset=0, group=None, global_pairs=None, sampler="ddpm", n_steps=50, eta=0.0):
+    sampler_timesteps(model, sampler, n_steps, eta, noise is not None and "steps" in noise)  # (raises before the module's mode changes)
     model.denoise_fn.eval()
     res = p_sample_loop_sliding_window_w_canonical(model, ds, x_start.shape, global_head_jpos, global_head_jquat,
                                                    cond_mask, noise=noise, parents=parents, window_offset=window_offset, group=group,
-                                                   global_pairs=global_pairs)
+                                                   global_pairs=global_pairs, sampler=sampler, n_steps=n_steps, eta=eta)
     model.denoise_fn.train()
     return res
 
 
 @torch.no_grad()
-def full_body_gen_cond_head_pose_sliding_window(model, ds, head_pose, noise=None, parents=None, window_offset=0, group=None, global_pairs=None):
-    """head_pose [B,T,7] = xyz + quaternion (w,x,y,z) -> (local axis-angle [B,T',22,3], root [B,T',3])."""
+def full_body_gen_cond_head_pose_sliding_window(model, ds, head_pose, noise=None, parents=None, window_offset=0, group=None, global_pairs=None,
+                                                sampler="ddpm", n_steps=50, eta=0.0):
+    """head_pose [B,T,7] = xyz + quaternion (w,x,y,z) -> (local axis-angle [B,T',22,3], root [B,T',3]).
+    sampler / n_steps / eta: the ancestral chain ("ddpm", the reference's) or the strided sampler per window ("ddim")."""
+    sampler_timesteps(model, sampler, n_steps, eta, noise is not None and "steps" in noise)  # (raises before any tensor is made)
     jpos, jquat = head_pose[:, :, :3], head_pose[:, :, 3:]
     data = torch.zeros(head_pose.shape[0], head_pose.shape[1], 198, device=head_pose.device)
     return sample_sliding_window_w_canonical(model, ds, jpos, jquat, data, prep_head_condition_mask(data), noise=noise,
-                                             parents=parents, window_offset=window_offset, group=group, global_pairs=global_pairs)
+                                             parents=parents, window_offset=window_offset, group=group, global_pairs=global_pairs,
+                                             sampler=sampler, n_steps=n_steps, eta=eta)
 
 
 # ------------------------------------------------------------------------------------------ ragged: many sequences, one batch
@@ -404,7 +463,7 @@ def ragged_window_table(num_frames_per_sequence, seq_len):
 
 @torch.no_grad()
 def full_body_gen_cond_head_pose_sliding_window_ragged(model, ds, head_poses, samples_per_sequence=1, noise=None, parents=None,
-                                                        sequence_offset=0, lengths=None):
+                                                        sequence_offset=0, lengths=None, sampler="ddpm", n_steps=50, eta=0.0):
     """full_body_gen_cond_head_pose_sliding_window over SEVERAL trajectories of different lengths at once: window index k runs ONCE,
     as one ragged batch (model/engine `lengths=`), for every (sequence, sample) pair that has a k-th window, instead of once per
     sequence — the sampler's step costs almost the same for 1 and for 100 windows.
@@ -421,7 +480,12 @@ def full_body_gen_cond_head_pose_sliding_window_ragged(model, ds, head_poses, sa
     alone through the one-sequence harness with window_offset = sequence_offset + s * n draws the same stream; `sequence_offset`
     is also what a sharded caller sets.  noise: a list of that harness's dicts, one per sequence ({'x_all': [n, T_s, D], 'cond':
     [per window [n, Tw, D]], optionally 'steps': [per window [S, n, Tw, D]]} — in every dict or in none), injects the draws (tests).
-    Unless every step is injected, model.sampling_rng = "torch" is not supported here (one generator cannot be consumed in every sequence's own order): set it to "philox"."""
+    Unless every step is injected, model.sampling_rng = "torch" is not supported here (one generator cannot be consumed in every sequence's own order): set it to "philox".
+    sampler="ddim": every window index runs the strided sampler over model.ddim_timesteps(n_steps) at `eta` (same prefix, lengths,
+    ids and seeds; injected 'steps' are [len(timesteps), n, Tw, D] per window).  At eta == 0 nothing is drawn per step, so any
+    sampling_rng will do."""
+    if sampler not in SAMPLERS:  # (before anything else: an unknown sampler is the caller's first mistake)
+        raise ValueError(f"unknown sampler {sampler!r}: one of {SAMPLERS} expected")
     if isinstance(head_poses, torch.Tensor):
         if lengths is None:
             raise ValueError("a padded head_poses tensor needs lengths")
@@ -439,9 +503,10 @@ def full_body_gen_cond_head_pose_sliding_window_ragged(model, ds, head_poses, sa
         raise ValueError("noise: either every sequence's dict carries 'steps' or none does "
                          f"(sequences with: {[s for s, w in enumerate(with_steps) if w]})")
     inject_steps = noise is not None and all(with_steps)
-    if not inject_steps and model.sampling_rng != "philox":  # (the per-step draws are then in-kernel Philox: never silently)
+    ts = sampler_timesteps(model, sampler, n_steps, eta, inject_steps)
+    if ts is None and not inject_steps and model.sampling_rng != "philox":  # (the per-step draws are then in-kernel Philox: never silently)
         raise ValueError(f'sampling_rng="{model.sampling_rng}" is not supported by the ragged sliding-window call: set model.sampling_rng = "philox"')
-    S, seq_len = model.num_timesteps, model.seq_len
+    S, seq_len = model.num_timesteps if ts is None else len(ts), model.seq_len  # S: steps per window
     stride = seq_len - OVERLAP
     frames = [int(h.shape[0]) for h in head_poses]
     table = ragged_window_table(frames, seq_len)  # (raises for a sequence without a window)
@@ -491,11 +556,16 @@ def full_body_gen_cond_head_pose_sliding_window_ragged(model, ds, head_poses, sa
         if k == 0:  # (the first window index's conditions shape stage 2 of the plan's measurement)
             eng = model.hip_engine(verify=True, job=job, conditions=x_cond)
         ragged = dict(lengths=wlen if min(wlen) < seq_len else None, window_ids=[sequence_offset + p for p in pairs])
-        if inject_steps:
+        if inject_steps and (ts is None or eta > 0):
             st = torch.zeros(S, bk, seq_len, D, device=device)
             for i, s in enumerate(ent["sequences"]):
                 st[:, i * n_smp:(i + 1) * n_smp, :ent["spans"][i][1]] = noise[s]["steps"][k].to(device).float()
-            eng.sample_loop_(curr_x, x_cond, S - 1, S, noise=st, prefix=pfx, **ragged)
+            if ts is None:
+                eng.sample_loop_(curr_x, x_cond, S - 1, S, noise=st, prefix=pfx, **ragged)
+            else:
+                eng.ddim_loop_(curr_x, x_cond, ts, eta=eta, noise=st, prefix=pfx, **ragged)
+        elif ts is not None:
+            eng.ddim_loop_(curr_x, x_cond, ts, eta=eta, seed=model.philox_seed + k, prefix=pfx, **ragged)
         else:
             eng.sample_loop_(curr_x, x_cond, S - 1, S, noise_mode=_lib.NOISE_PHILOX, seed=model.philox_seed + k, prefix=pfx, **ragged)
         model._note_job((bk, seq_len, S))

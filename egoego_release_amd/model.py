@@ -595,12 +595,24 @@ class CondGaussianDiffusion(nn.Module):
         self.denoise_fn.train()
         return res
 
+    def ddim_timesteps(self, n_steps):
+        """The strided sampler's timestep list: n_steps points uniform over 0..num_timesteps-1, rounded, de-duplicated, descending
+        (it always ends at 0; fewer than n_steps entries when n_steps exceeds what the schedule can tell apart)."""
+        return sorted({int(round(v)) for v in np.linspace(0, self.num_timesteps - 1, n_steps)}, reverse=True)
+
     @torch.no_grad()
-    def ddim_sample(self, x_start, cond_mask, n_steps=50, noise=None, eta=0.0):
+    def ddim_sample(self, x_start, cond_mask, n_steps=50, noise=None, eta=0.0, lengths=None, prefix=None):
         """DDIM on a uniform stride of the training timesteps (eta=0: deterministic; eta > 0 draws in-kernel Philox
         noise keyed by `philox_seed`; eta=1 with n_steps=num_timesteps is the ancestral chain).  Not part of the
-        reference (it only has the full ancestral chain); provided for BASELINE config 4."""
-        job = (int(x_start.shape[0]), int(x_start.shape[1]), int(n_steps))
+        reference (it only has the full ancestral chain); provided for BASELINE config 4.
+
+        lengths (optional, [B], each 1..T): a RAGGED batch, as for p_sample_loop — every window is sampled at its own length and its
+        frames past it come back as zeros.  prefix (optional, [B, P, D]): the first P frames of every window are re-imposed after
+        every step (the sliding-window in-painting, imposed clean as the reference does for its own chain)."""
+        if lengths is not None:  # (bad host values raise here, before the draws and the measurement)
+            lengths = engine_mod.check_lengths(lengths, int(x_start.shape[0]), int(x_start.shape[1]), 0 if prefix is None else int(prefix.shape[1]))
+        ts = self.ddim_timesteps(n_steps)
+        job = (int(x_start.shape[0]), int(x_start.shape[1]), len(ts))
         device = self.betas.device
         if device.type != "cuda":
             self.hip_engine()  # (raises: no CPU path)
@@ -610,10 +622,12 @@ class CondGaussianDiffusion(nn.Module):
             x, cn = torch.randn(x_start.shape, device=device), torch.randn_like(x_start)
         x_cond = self._f32c(x_start * (1.0 - cond_mask) + cond_mask * cn)
         eng = self.hip_engine(verify=True, job=job, conditions=x_cond)
-        ts = sorted({int(round(v)) for v in np.linspace(0, self.num_timesteps - 1, n_steps)}, reverse=True)
-        eng.ddim_loop_(x, x_cond, ts, eta=eta, seed=self.philox_seed)
+        eng.ddim_loop_(x, x_cond, ts, eta=eta, seed=self.philox_seed, prefix=None if prefix is None else self._f32c(prefix), lengths=lengths)
         self._note_job(job)
         self._outlier_guard(eng, x, x_cond)
+        if lengths is not None:  # frames past a window's length: computed (unspecified), returned as zeros
+            lt = torch.as_tensor(lengths).to(x.device)
+            x.mul_((torch.arange(x.shape[1], device=x.device)[None, :] < lt[:, None]).to(x.dtype)[:, :, None])
         return x
 
     # ------------------------------------------------------------------ sliding-window harness (harness.py)
@@ -623,19 +637,22 @@ class CondGaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop_sliding_window_w_canonical(self, ds, shape, global_head_jpos, global_head_jquat, cond_mask, noise=None,
-                                                 parents=None):
+                                                 parents=None, sampler="ddpm", n_steps=50, eta=0.0):
         from . import harness
         return harness.p_sample_loop_sliding_window_w_canonical(self, ds, shape, global_head_jpos, global_head_jquat,
-                                                                cond_mask, noise=noise, parents=parents)
+                                                                cond_mask, noise=noise, parents=parents, sampler=sampler,
+                                                                n_steps=n_steps, eta=eta)
 
     @torch.no_grad()
     def sample_sliding_window_w_canonical(self, ds, global_head_jpos, global_head_jquat, x_start, cond_mask, noise=None,
-                                          parents=None, window_offset=0):
+                                          parents=None, window_offset=0, sampler="ddpm", n_steps=50, eta=0.0):
         """`parents` (or `ds.parents`) overrides the SMPL-H kintree the conversion chain walks;
-        `window_offset`: global index of sequence 0 (dist.harness_sharded)."""
+        `window_offset`: global index of sequence 0 (dist.harness_sharded).  sampler="ddim": every window runs the strided
+        sampler over ddim_timesteps(n_steps) at `eta` instead of the ancestral chain (harness.py)."""
         from . import harness
         return harness.sample_sliding_window_w_canonical(self, ds, global_head_jpos, global_head_jquat, x_start, cond_mask,
-                                                         noise=noise, parents=parents, window_offset=window_offset)
+                                                         noise=noise, parents=parents, window_offset=window_offset,
+                                                         sampler=sampler, n_steps=n_steps, eta=eta)
 
     # ------------------------------------------------------------------ training half (plain PyTorch)
     def q_sample(self, x_start, t, noise=None):

@@ -200,7 +200,8 @@ int egoego_sample_loop(egoego_ctx* ctx, float* d_x, const float* d_x_cond, int t
  * selection is that of the padded (B, T): a short window costs what a full one does.
  * One captured step serves every ragged call of a shape on a workspace (the arrays are step state, never graph arguments); uniform
  * and ragged calls of the same shape keep separate graphs (they launch different kernel instantiations).
- * NOT ragged: egoego_ddim_loop and egoego_debug_stage take one T for the whole batch. */
+ * The strided sampler has its ragged form too (egoego_ddim_loop_ragged, below).  NOT ragged: egoego_debug_stage takes one T for
+ * the whole batch. */
 int egoego_denoise_ragged(egoego_ctx* ctx, const float* d_x, const float* d_x_cond, const int64_t* d_t,
                           const float* d_row_mask, const int32_t* d_lengths, float* d_out, int B, int T,
                           void* d_workspace, size_t workspace_bytes, void* stream);
@@ -222,6 +223,23 @@ int egoego_sample_loop_ragged(egoego_ctx* ctx, float* d_x, const float* d_x_cond
 int egoego_ddim_loop(egoego_ctx* ctx, float* d_x, const float* d_x_cond, const int32_t* timesteps_host, int n,
                      float eta, const float* d_noise, int noise_mode, uint64_t seed, int64_t window_offset,
                      int B, int T, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* egoego_ddim_loop through the sliding-window harnesses: the same chain plus the five arguments egoego_sample_loop_ragged adds to
+ * egoego_sample_loop, with the same meaning and lifetime rules (the ABI version stays 8: purely additive).
+ *   d_prefix / prefix_len  the first prefix_len frames of every window are overwritten with d_prefix[B][prefix_len][D] after EVERY
+ *                          step, the last included (M:395-397).  The prefix is imposed clean, as the reference does for its own
+ *                          chain: no noise-matched in-painting.  prefix_len in 1..T when d_prefix is given; NULL: none.
+ *   d_row_mask             fp32 [B][T+1] padding mask handed to every step, or NULL.
+ *   d_lengths, d_window_ids  as for the ragged entry points above: DEVICE arrays read through the step state, never graph
+ *                          arguments, so one captured step serves every later call of that (B, T, noise mode, prefix_len, mask,
+ *                          ragged) shape on a workspace, whatever its timestep list, arrays and buffers.
+ * Per-step Philox draws stay keyed by the actual timestep: an eta > 0 strided chain draws, at timestep t, the stream the ancestral
+ * chain draws there.  With d_prefix, d_row_mask, d_lengths and d_window_ids all NULL this is egoego_ddim_loop, bit for bit. */
+int egoego_ddim_loop_ragged(egoego_ctx* ctx, float* d_x, const float* d_x_cond, const int32_t* timesteps_host, int n,
+                            float eta, const float* d_noise, int noise_mode, uint64_t seed, int64_t window_offset,
+                            const float* d_prefix, int prefix_len, const float* d_row_mask,
+                            const int32_t* d_lengths, const int64_t* d_window_ids, int B, int T,
+                            void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Replaces pytorch3d.transforms.rotation_6d_to_matrix at M:493: d_in [n][6] -> d_out [n][3][3]. */
 int egoego_rot6d_to_matrix(const float* d_in, float* d_out, int64_t n, void* stream);

@@ -9,7 +9,8 @@
   --data_root_folder    the reference's ARES demo layout (demo_ares_data.p, droid_slam_res/, <scene>/<seq>/raft_of_feats/)
   --weight_root_folder  stage1_headnet_ares_250.pt, stage1_gravitynet_2000.pt, stage2_diffusion_4.pt (run_egoego.py:57-85); a
                         missing file means seeded synthetic weights for that network (listed in the report)
-  --stats / --rest_offsets / --timesteps / --seed  as in tools/run_stage2_demo.py
+  --stats / --rest_offsets / --timesteps / --seed / --ddim_steps / --ddim_eta  as in tools/run_stage2_demo.py (--ddim_eta > 0
+                        switches stage 2's per-step noise to the in-kernel Philox stream keyed by --seed)
 
 Writes an npz with the stage-1 head pose [B, T, 7], the local axis-angle [B, T', 22, 3], the root [B, T', 3] and the global joints
 [B, T', 22, 3], and prints one JSON line with the stage-1 and stage-2 wall times.  The floor-height shift of run_egoego.py:161-173
@@ -83,6 +84,8 @@ def parse_opt(argv=None):
     p.add_argument("--stats", required=True)
     p.add_argument("--rest_offsets", required=True)
     p.add_argument("--timesteps", type=int, default=1000, help="diffusion steps (lower = truncated chain, for smoke runs)")
+    p.add_argument("--ddim_steps", type=int, default=0, help="N > 0: the strided DDIM sampler over N timesteps per window (0 = the ancestral chain)")
+    p.add_argument("--ddim_eta", type=float, default=0.0, help="DDIM noise weight in [0, 1]; > 0 draws in-kernel Philox noise keyed by --seed")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", default="egoego_out.npz")
     return p.parse_args(argv)
@@ -138,10 +141,15 @@ def gen_full_body_vis(bm_dict, root_trans, local_aa, mesh_folder):
 
 def main(argv=None):
     opt = parse_opt(argv)
+    if opt.ddim_steps < 0 or not 0.0 <= opt.ddim_eta <= 1.0:
+        raise SystemExit("--ddim_steps must be >= 0 and --ddim_eta in [0, 1]")
+    sampler = dict(sampler="ddim", n_steps=opt.ddim_steps, eta=opt.ddim_eta) if opt.ddim_steps else {}
     dev = torch.device("cuda", int(opt.device))
     torch.cuda.set_device(dev)
     hn, gn, notes = build_stage1(opt, dev)
     model, notes[DIFFUSION_FILE] = build_stage2(opt, dev)
+    if opt.ddim_steps and opt.ddim_eta > 0:  # (the strided sampler has no reference draw order to reproduce: its noise is drawn in-kernel)
+        model.sampling_rng, model.philox_seed = "philox", opt.seed
     stats = S2._load_any(opt.stats)
     ds = harness.SkeletonStats(stats["global_jpos_min"], stats["global_jpos_max"], np.load(opt.rest_offsets), harness.SMPLH_PARENTS_22)
     batches = stage1.load_ares_demo(opt.data_root_folder)
@@ -164,7 +172,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         b = time.perf_counter()
         rep_hp = hp.repeat_interleave(opt.diffusion_batch_size, 0)  # run_egoego.py:147
-        aa, root = harness.full_body_gen_cond_head_pose_sliding_window(model, ds, rep_hp)
+        aa, root = harness.full_body_gen_cond_head_pose_sliding_window(model, ds, rep_hp, **sampler)
         n, t = aa.shape[:2]
         _, gj = ds.fk_smpl(root.reshape(-1, 3), aa.reshape(-1, 22, 3))
         gj = gj.reshape(n, t, 22, 3)
@@ -194,7 +202,8 @@ def main(argv=None):
                 mesh = {"mesh_verts": vt.cpu().numpy(), "mesh_jnts": jn.cpu().numpy(), "mesh_shift": -move[0, 0, 0].cpu().numpy()}
     np.savez_compressed(opt.out, **{k: np.concatenate(v) for k, v in out.items()}, **mesh)
     rep = {"sequences": names, "frames": int(out["head_pose"][0].shape[1]), "samples": opt.diffusion_batch_size,
-           "stage1_seconds": round(t1, 4), "stage2_seconds": round(t2, 4), "diffusion_steps": opt.timesteps, "weights": notes,
+           "stage1_seconds": round(t1, 4), "stage2_seconds": round(t2, 4), "diffusion_steps": opt.timesteps, "ddim_steps": opt.ddim_steps,
+           "ddim_eta": opt.ddim_eta, "weights": notes,
            "not_done": ["get_head_vel", "visualisation"],
            "out": opt.out}
     if vis:

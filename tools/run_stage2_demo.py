@@ -26,6 +26,9 @@ of this repo: every asset is an input file, and without `--w
                   compute_metrics_for_smpl per sample (egoego_release_amd.evaluate, on the device; the foot sliding of the samples
                   is measured from each sample's own floor height, the ground truth's from 0)
   --gt_quat       optional .npy [T,22,4] ground-truth global rotations (w,x,y,z): adds the root / head rotation keys
+  --ddim_steps N  N > 0: every window runs the strided DDIM sampler over N timesteps (model.ddim_timesteps) instead of the
+                  reference's ancestral chain over all --timesteps (0, the default); --ddim_eta in [0, 1] weights its per-step
+                  noise (0 = deterministic; > 0 draws in-kernel, so it needs --sampling_rng philox).  Not in the reference
 """
 import argparse
 import json
@@ -94,6 +97,8 @@ def parse_opt(argv=None):
     p.add_argument("--gt_quat", default="")
     p.add_argument("--timesteps", type=int, default=1000, help="diffusion steps (lower = truncated chain, for smoke runs)")
     p.add_argument("--sampling_rng", default="torch", choices=("torch", "philox"))
+    p.add_argument("--ddim_steps", type=int, default=0, help="N > 0: the strided DDIM sampler over N timesteps per window (0 = the ancestral chain)")
+    p.add_argument("--ddim_eta", type=float, default=0.0, help="DDIM noise weight in [0, 1]; > 0 needs --sampling_rng philox")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--noise", default="", help="torch-saved dict {'x_all','cond','steps'} of injected draws (harness.py "
                                                "p_sample_loop_sliding_window_w_canonical): reproducibility / parity runs")
@@ -135,6 +140,11 @@ def main(argv=None):
         raise SystemExit("several --head_pose files run the single-process ragged call: --gpus, --gt_jpos and --noise take one trajectory")
     if not several:
         opt.head_pose = opt.head_pose[0]
+    if opt.ddim_steps < 0 or not 0.0 <= opt.ddim_eta <= 1.0:
+        raise SystemExit("--ddim_steps must be >= 0 and --ddim_eta in [0, 1]")
+    if opt.ddim_steps and opt.ddim_eta > 0 and opt.sampling_rng != "philox" and not several and not (opt.noise and opt.gpus < 1):
+        raise SystemExit("--ddim_eta > 0 draws its per-step noise in-kernel: add --sampling_rng philox")
+    sampler = dict(sampler="ddim", n_steps=opt.ddim_steps, eta=opt.ddim_eta) if opt.ddim_steps else {}
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(opt.gpus, sys.argv[1:] if argv is None else argv)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -179,7 +189,7 @@ def main(argv=None):
         # sequence-sharded: every (trajectory, sample) pair stays on one rank (its windows depend on each other), one all_gather at the end
         from egoego_release_amd import dist as D
         head_pose = load_head_pose(opt.head_pose)
-        aa, root = D.harness_sharded(model, ds, head_pose, sample_bs=opt.diffusion_batch_size, seed=opt.seed, parents=parents)
+        aa, root = D.harness_sharded(model, ds, head_pose, sample_bs=opt.diffusion_batch_size, seed=opt.seed, parents=parents, **sampler)
         head_pose = head_pose.repeat_interleave(opt.diffusion_batch_size, 0)
     elif several:
         # trajectories of different lengths: every window index runs once for all of them (the per-step draws are in-kernel Philox)
@@ -191,11 +201,11 @@ def main(argv=None):
             poses.append(hp[0].to(dev))
         model.sampling_rng = "philox"
         aa, root, out_lengths = harness.full_body_gen_cond_head_pose_sliding_window_ragged(model, ds, poses,
-                                                                                           samples_per_sequence=opt.diffusion_batch_size)
+                                                                                           samples_per_sequence=opt.diffusion_batch_size, **sampler)
     else:
         head_pose = load_head_pose(opt.head_pose).repeat_interleave(opt.diffusion_batch_size, 0).to(dev)
         noise = torch.load(opt.noise, map_location="cpu") if opt.noise else None
-        aa, root = harness.full_body_gen_cond_head_pose_sliding_window(model, ds, head_pose, noise=noise)
+        aa, root = harness.full_body_gen_cond_head_pose_sliding_window(model, ds, head_pose, noise=noise, **sampler)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     if dist is not None:
@@ -214,13 +224,13 @@ def main(argv=None):
         out["out_lengths"] = out_lengths.numpy()
         rep = {"frames": [int(v) for v in out_lengths], "samples": int(b), "sequences": len(poses),
                "windows": sum(len(harness.window_spans(int(p.shape[0]), opt.diffusion_window)) for p in poses) * opt.diffusion_batch_size,
-               "diffusion_steps": opt.timesteps, "seconds": round(el, 3), "checkpoint": info, "ranks": world, "sharding": None,
+               "diffusion_steps": opt.timesteps, "ddim_steps": opt.ddim_steps, "ddim_eta": opt.ddim_eta, "seconds": round(el, 3), "checkpoint": info, "ranks": world, "sharding": None,
                "ragged": True}
         np.savez_compressed(opt.out, **out)
         print(json.dumps(rep), flush=True)
         return rep
     rep = {"frames": int(t), "samples": int(b), "windows": len(range(0, head_pose.shape[1], opt.diffusion_window - harness.OVERLAP)),
-           "diffusion_steps": opt.timesteps, "seconds": round(el, 3), "checkpoint": info, "ranks": world,
+           "diffusion_steps": opt.timesteps, "ddim_steps": opt.ddim_steps, "ddim_eta": opt.ddim_eta, "seconds": round(el, 3), "checkpoint": info, "ranks": world,
            "sharding": "by sequence (dist.harness_sharded)" if opt.gpus >= 1 else None}
     if opt.gt_jpos:
         gt = np.load(opt.gt_jpos)
