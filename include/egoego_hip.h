@@ -35,6 +35,17 @@
  *     captured step graphs are shared by every call of a shape, and the per-workspace step state (timestep counters, the
  *     caller's buffer pointers, the Philox key) is rewritten by every loop call — two streams driving one workspace or one
  *     context concurrently race silently.  Use one context + workspace per stream.
+ *   - workspace contents: what a workspace holds ON ENTRY is irrelevant to every result of every entry point that takes one
+ *     (egoego_denoise / _p_sample / _sample_loop / _ddim_loop and their _ragged forms, egoego_debug_stage, egoego_s1_encode,
+ *     egoego_flow_features, egoego_body_forward, egoego_win_stats): any bytes will do — zeros, NaN or infinity patterns, what an
+ *     earlier call of another shape left — and the same call gives the same bits.  No value that a kernel uses as an index, a
+ *     count, a timestep or an address is read before the same call has written it; stale values are only ever read as DATA of
+ *     rows, keys or frames that are never stored (DESIGN.md 4a lists every region with its writer).  A workspace needs no
+ *     clearing before use and may be shared by calls of different shapes, one after the other.
+ *     The ONE exception is the stage-2 outlier monitor (StepState::ln_max, the first bytes of a stage-2 workspace): it
+ *     accumulates over calls by design and is read only by egoego_outlier_stats.  Establish it with
+ *     egoego_outlier_stats(ctx, B, T, ws, bytes, NULL, 0, 1, stream) on a workspace that is new or whose bytes were overwritten
+ *     from outside (engine.py does for each buffer it allocates); no sampling result depends on it.
  */
 #ifndef EGOEGO_HIP_H
 #define EGOEGO_HIP_H
