@@ -25,6 +25,7 @@ class ContextEngine:
         self.device = torch.device("cuda", self.dev_index)
         self._ctx = C.c_void_p()
         self._ws = None
+        self._ws_home = None  # the stream self._ws was allocated under
 
     def _create(self, *args):
         type(self).CHECK(getattr(self.lib, self.CREATE)(*args, C.byref(self._ctx)))
@@ -33,12 +34,19 @@ class ContextEngine:
         return C.c_void_p(torch.cuda.current_stream(self.dev_index).cuda_stream)
 
     def _workspace(self, *shape):
-        """The workspace of a call of this shape -> (pointer aligned to 256 bytes, bytes from there); the buffer only grows."""
+        """The workspace of a call of this shape on the current stream -> (pointer aligned to 256 bytes, bytes from there); the
+        buffer only grows.  The caching allocator orders a freed block against the stream it was allocated under only: a buffer
+        handed to the library under another stream is recorded on that stream, so that dropping it when it grows cannot give its
+        memory to a later allocation while that stream still works in it."""
         n = getattr(self.lib, self.WORKSPACE_BYTES)(self._ctx, *shape)
         if n == 0:
             raise _lib.EgoEgoHipError(type(self).CHECK.last_error())
+        stream = torch.cuda.current_stream(self.dev_index)
         if self._ws is None or self._ws.numel() < n + 256:
             self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            self._ws_home = stream
+        elif stream != self._ws_home:
+            self._ws.record_stream(stream)
         off = (-self._ws.data_ptr()) % 256
         return self._ws.data_ptr() + off, self._ws.numel() - off
 

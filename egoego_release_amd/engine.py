@@ -82,6 +82,7 @@ class HipEngine:
         self._ctx = C.c_void_p()
         _lib.check(self.lib.egoego_ctx_create(C.byref(c), self.dev_index, C.byref(self._ctx)))
         self._ws = {}
+        self._ws_home = {}  # (B, T) -> the stream its buffer was allocated under
         self.load(state_dict)
 
     # ------------------------------------------------------------------ weights
@@ -135,19 +136,28 @@ class HipEngine:
         return C.c_void_p(torch.cuda.current_stream(self.dev_index).cuda_stream)
 
     def workspace(self, B, T):
+        """The cached workspace of a shape -> (pointer aligned to 256 bytes, bytes from there), for a call on the current stream.
+        The caching allocator orders a freed block against the stream it was allocated under only: a buffer handed to the library
+        under another stream is recorded on that stream, so that dropping it (the fifth shape, close()) cannot give its memory
+        to a later allocation while that stream still works in it."""
         key = (B, T)
         ws = self._ws.get(key)
+        stream = torch.cuda.current_stream(self.dev_index)
         if ws is None:
             n = self.lib.egoego_workspace_bytes(self._ctx, B, T)
             if n == 0:
                 raise _lib.EgoEgoHipError(f"unsupported shape B={B} T={T}: {self.lib.egoego_last_error().decode()}")
             if len(self._ws) >= 4:
                 self._ws.clear()
+                self._ws_home.clear()
             ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
             self._ws[key] = ws
+            self._ws_home[key] = stream
             off = (-ws.data_ptr()) % 256
             # a fresh workspace holds undefined bytes: clear its outlier monitor (no sync)
             _lib.check(self.lib.egoego_outlier_stats(self._ctx, B, T, ws.data_ptr() + off, ws.numel() - off, None, 0, 1, self._stream()))
+        elif stream != self._ws_home[key]:
+            ws.record_stream(stream)
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
 
@@ -324,6 +334,7 @@ class HipEngine:
             self.lib.egoego_ctx_destroy(self._ctx)
             self._ctx = C.c_void_p()
         self._ws = {}
+        self._ws_home = {}
 
     def __del__(self):
         try:
