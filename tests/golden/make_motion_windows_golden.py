@@ -50,8 +50,40 @@ RUNS = ((120, True), (120, False), (40, True), (40, False))
 ITEM_WINDOWS = 2  # __getitem__ items stored per run: the first full window and the first padded one
 
 
-def sample_rows(length):
-    return np.array([t for t in range(length) if t % ROW_STEP == 0 or t >= length - 2])
+def sample_rows(length, step=ROW_STEP):
+    return np.array([t for t in range(length) if t % step == 0 or t >= length - 2])
+
+
+def stand_in_dataset(DS, rest_offsets, data_dict, window, cano):
+    """The stand-in `self`: the reference's own AMASSDataset methods bound to an object that carries what they read.
+    process_window_data also returns local_rot_6d, which cal_normalize_data_input drops: it is wrapped to record it in
+    ds.local6d (nothing is changed)."""
+    ds = types.SimpleNamespace(opt=types.SimpleNamespace(canonicalize_init_head=cano), window=window, data_dict=data_dict,
+                               rest_human_offsets=torch.from_numpy(rest_offsets).float().reshape(1, 22, 3), local6d=[])
+    for name in ("cal_normalize_data_input", "process_window_data", "extract_min_max_mean_std_from_data", "__getitem__",
+                 "normalize_jpos_min_max", "__len__"):
+        setattr(ds, name, types.MethodType(getattr(DS.AMASSDataset, name), ds))
+    pwd0 = ds.process_window_data
+
+    def pwd_rec(*a, **k):
+        q = pwd0(*a, **k)
+        ds.local6d.append(q["local_rot_6d"].reshape(-1, 132).numpy().copy())
+        return q
+    ds.process_window_data = pwd_rec
+    return ds
+
+
+def record_headings(DS):
+    """Wraps DS.rotate_at_frame_smplh to record the heading it returns -> the list that fills up."""
+    yrots = []
+    raf0 = DS.rotate_at_frame_smplh
+
+    def raf_rec(*a, **k):
+        res = raf0(*a, **k)
+        yrots.append(np.array(res[2]).reshape(4))
+        return res
+    DS.rotate_at_frame_smplh = raf_rec
+    return yrots
 
 
 def main():
@@ -71,15 +103,7 @@ def main():
                  for k, s in enumerate(seqs)}
     out["seq_names"] = np.array([data_dict[k]["seq_name"] for k in data_dict])
 
-    yrots = []
-    raf0 = DS.rotate_at_frame_smplh
-
-    def raf_rec(*a, **k):
-        res = raf0(*a, **k)
-        yrots.append(np.array(res[2]).reshape(4))
-        return res
-    DS.rotate_at_frame_smplh = raf_rec
-
+    yrots = record_headings(DS)
     worst = {}
 
     def note(key, ref, orc):
@@ -88,20 +112,8 @@ def main():
 
     for window, cano in RUNS:
         tag = "w%d_%s" % (window, "cano" if cano else "raw")
-        ds = types.SimpleNamespace(opt=types.SimpleNamespace(canonicalize_init_head=cano), window=window, data_dict=data_dict,
-                                   rest_human_offsets=torch.from_numpy(REST_OFFSETS).float().reshape(1, 22, 3))
-        for name in ("cal_normalize_data_input", "process_window_data", "extract_min_max_mean_std_from_data", "__getitem__",
-                     "normalize_jpos_min_max", "__len__"):
-            setattr(ds, name, types.MethodType(getattr(DS.AMASSDataset, name), ds))
-        # process_window_data also returns local_rot_6d, which cal_normalize_data_input drops: record it (nothing is changed)
-        local6d = []
-        pwd0 = ds.process_window_data
-
-        def pwd_rec(*a, **k):
-            q = pwd0(*a, **k)
-            local6d.append(q["local_rot_6d"].reshape(-1, 132).numpy().copy())
-            return q
-        ds.process_window_data = pwd_rec
+        ds = stand_in_dataset(DS, REST_OFFSETS, data_dict, window, cano)
+        local6d = ds.local6d
         del yrots[:]
         ds.cal_normalize_data_input()
         wd = ds.window_data_dict

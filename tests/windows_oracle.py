@@ -110,6 +110,9 @@ def build(seqs, rest_offsets, window=120, canonicalize=True, min_frames=30, tabl
     out = {"global_jpos": np.zeros((N, window, 66)), "global_jvel": np.zeros((N, window, 66)), "global_rot_6d": np.zeros((N, window, 132)),
            "local_rot_6d": np.zeros((N, window, 132)), "recover_rot_quat": np.zeros((N, 4))}
     for i, (k, start, _, length) in enumerate(table):
+        if length == 0:  # an empty window (only through `table`): no first frame, so no heading; zero rows
+            out["recover_rot_quat"][i] = [1.0, 0.0, 0.0, 0.0]
+            continue
         w = process_window(*(a[start:start + length] for a in seqs[k]), rest_offsets, canonicalize)
         for key in KEYS[:4]:
             out[key][i, :length] = w[key]
