@@ -41,6 +41,10 @@ class ContextEngine:
         n = getattr(self.lib, self.WORKSPACE_BYTES)(self._ctx, *shape)
         if n == 0:
             raise _lib.EgoEgoHipError(type(self).CHECK.last_error())
+        return self._workspace_of(n)
+
+    def _workspace_of(self, n):
+        """_workspace for a byte count the caller already holds (a module without a context asks its own query)."""
         stream = torch.cuda.current_stream(self.dev_index)
         if self._ws is None or self._ws.numel() < n + 256:
             self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)

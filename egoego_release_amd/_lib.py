@@ -88,7 +88,9 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_eval_last_error", "egoego_eval_max_frames", "egoego_eval_fk", "egoego_eval_shift_xy",
            "egoego_eval_floor_contacts", "egoego_eval_metrics", "egoego_eval_root_to_floor", "egoego_eval_best",
            "egoego_win_last_error", "egoego_win_max_window", "egoego_win_build", "egoego_win_stats_workspace_bytes", "egoego_win_stats",
-           "egoego_win_motion"]
+           "egoego_win_motion",
+           "egoego_amass_last_error", "egoego_amass_max_frames", "egoego_amass_joints", "egoego_amass_floor_workspace_bytes",
+           "egoego_amass_floor_contacts", "egoego_amass_head"]
 EVAL_METRIC_KEYS = ("root_dist", "root_rot_dist", "root_trans_dist", "head_dist", "head_rot_dist", "head_trans_dist", "mpjpe",
                     "mpjpe_wo_hand", "accel_pred", "accel_gt", "accel_err", "pred_fs", "gt_fs")  # then single_jpe[22]
 EVAL_N_METRICS = len(EVAL_METRIC_KEYS) + 22
@@ -194,6 +196,13 @@ def load():
     lib.egoego_win_stats_workspace_bytes.restype = sz
     lib.egoego_win_stats.argtypes = [vp, vp, vp, i32, i32, vp, vp, sz, vp]
     lib.egoego_win_motion.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.egoego_amass_last_error.restype = C.c_char_p
+    lib.egoego_amass_max_frames.restype = i32
+    lib.egoego_amass_joints.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int32), i32, vp, vp, vp]
+    lib.egoego_amass_floor_workspace_bytes.argtypes = [i32, i32]
+    lib.egoego_amass_floor_workspace_bytes.restype = sz
+    lib.egoego_amass_floor_contacts.argtypes = [vp, C.POINTER(C.c_int32), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.egoego_amass_head.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -220,3 +229,4 @@ check_flow = _checker("flow-CNN ", "egoego_flow_last_error")
 check_body = _checker("body-model ", "egoego_body_last_error")
 check_eval = _checker("evaluation ", "egoego_eval_last_error")
 check_win = _checker("motion-window ", "egoego_win_last_error")
+check_amass = _checker("AMASS-preprocessing ", "egoego_amass_last_error")

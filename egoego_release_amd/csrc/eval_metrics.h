@@ -30,29 +30,13 @@
 //      gather the root heights, and a rank count for the middle ones.  It runs for the floor group and for the groups that pass
 //      the two cheap tests (median height, size) only;
 //   7. contacts from the velocity flags and the heights above floor_height (not the offset height).
+// The thresholds, the contact joints and the LDS layout live in floor_common.h, which amass_prep.h's floor kernel shares.
 #pragma once
 #include "common.h"
 #include "quat_f64.h"
+#include "floor_common.h"
 
 namespace evalm {
-
-static constexpr int NJ = 22;
-static constexpr int FRAME_BITS = 12;
-static constexpr int MAX_T = 1 << FRAME_BITS;  // 4096 frames: 2 T samples of 4 + 4 + 4 bytes and the group tables fill 153 of 160 KiB
-static constexpr int FC_THREADS = 1024;
-static constexpr int FC_ELEMS = 2 * MAX_T / FC_THREADS;  // sorted samples per thread, at most
-static constexpr int MT_THREADS = 256;
-static constexpr int N_ACC = 11 + NJ;
-static constexpr int N_METRICS = 13 + NJ;
-static constexpr int HEAD = 15;
-
-static constexpr double VEL_THRESH = 0.005;  // FLOOR_VEL_THRESH = CONTACT_VEL_THRESH
-static constexpr double DB_EPS = 0.005;
-static constexpr float TOE_H = 0.04f, ANKLE_H = 0.08f;  // CONTACT_TOE_HEIGHT_THRESH, CONTACT_ANKLE_HEIGHT_THRESH
-static constexpr float TERRAIN_H = 0.04f, ROOT_H = 0.04f, FLOOR_OFFSET = 0.01f;
-// the eight joints with a contact channel, toes first: bit k of a frame's flags belongs to contact_joint(k)
-// (left / right toe base, foot, hand, leg of body_model/utils.py:5-8)
-EG_HD constexpr int contact_joint(int k) { return k == 0 ? 10 : k == 1 ? 11 : k == 2 ? 7 : k == 3 ? 8 : k == 4 ? 20 : k == 5 ? 21 : k == 6 ? 4 : 5; }
 
 // ---------------------------------------------------------------- forward kinematics
 struct FkArgs {
@@ -153,26 +137,6 @@ struct FloorArgs {
     int B, T, size_thresh, cap;  // cap: power of two >= max(2 T, 64), fixes the LDS layout
 };
 
-// LDS layout for a given cap, shared by host and device
-struct FloorLds {
-    size_t sh, sp, lab, gmed, gsz, rootv, vf, mask, part, total;
-};
-EG_HD FloorLds floor_lds(int cap) {
-    FloorLds l;
-    size_t o = 0;
-    l.sh = o;    o += (size_t)cap * 4;
-    l.sp = o;    o += (size_t)cap * 4;
-    l.lab = o;   o += (size_t)cap * 4;
-    l.gmed = o;  o += ((size_t)cap / 2 + 2) * 4;
-    l.gsz = o;   o += ((size_t)cap / 2 + 2) * 4;
-    l.rootv = o; o += (size_t)cap / 2 * 4;
-    l.mask = o;  o += ((size_t)cap / 64 + 1) * 4;
-    l.part = o;  o += (size_t)FC_THREADS * 4;
-    l.vf = o;    o += (size_t)cap / 2;
-    l.total = (o + 15) / 16 * 16;
-    return l;
-}
-
 // Exclusive prefix sum of flag(i), i < n, over the block: emit(i, prefix, flag(i)) for every i, returns the total.  A thread owns
 // a contiguous run of ceil(n / threads) <= 32 entries and evaluates each flag once, before any emit runs.
 template <typename F, typename E>
@@ -200,8 +164,6 @@ EG_D int block_scan(int n, int* part, F flag, E emit) {
     __syncthreads();
     return total;
 }
-
-EG_D bool within_eps(float a, float b) { return fabs((double)a - (double)b) <= DB_EPS; }
 
 // the median (fp32, numpy's) of the root heights of the unique frames of the samples labelled `label`
 EG_D float root_median(int label, int n, int L, const float* P, const uint32_t* sp, const int* lab, uint32_t* mask, float* rootv, int* part,

@@ -37,7 +37,7 @@
  *     context concurrently race silently.  Use one context + workspace per stream.
  *   - workspace contents: what a workspace holds ON ENTRY is irrelevant to every result of every entry point that takes one
  *     (egoego_denoise / _p_sample / _sample_loop / _ddim_loop and their _ragged forms, egoego_debug_stage, egoego_s1_encode,
- *     egoego_flow_features, egoego_body_forward, egoego_win_stats): any bytes will do — zeros, NaN or infinity patterns, what an
+ *     egoego_flow_features, egoego_body_forward, egoego_win_stats, egoego_amass_floor_contacts): any bytes will do — zeros, NaN or infinity patterns, what an
  *     earlier call of another shape left — and the same call gives the same bits.  No value that a kernel uses as an index, a
  *     count, a timestep or an address is read before the same call has written it; stale values are only ever read as DATA of
  *     rows, keys or frames that are never stored (DESIGN.md 4a lists every region with its writer).  A workspace needs no
@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*), the motion windows (egoego_win_*) and the ragged sampling entry points (egoego_*_ragged) were added under 8: purely additive, no existing entry changed */
+#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*), the motion windows (egoego_win_*), the ragged sampling entry points (egoego_*_ragged) and the AMASS preprocessing (egoego_amass_*) were added under 8: purely additive, no existing entry changed */
 
 enum {
     EGOEGO_OK = 0,
@@ -555,6 +555,47 @@ int egoego_win_stats(const float* d_jpos, const float* d_jvel, const int32_t* d_
  * divides by zero, as in the reference), then d_grot6d; zero rows past each length. */
 int egoego_win_motion(const float* d_jpos, const float* d_grot6d, const int32_t* d_length, const float* d_jpos_min, const float* d_jpos_max,
                       int N, int W, float* d_motion, void* stream);
+
+/* ==================================================================================================================
+ * AMASS preprocessing (egoego_amass_*; added under ABI 8, purely additive): raw AMASS sequences -> the records of the reference's
+ * process_seq (utils/data_utils/process_amass_dataset.py:340-493).  Every tensor is a device tensor unless it says host.  The raw
+ * frames of all B sequences are packed end to end ([N] rows): sequence b owns rows offsets[b] .. offsets[b + 1], offsets[0] = 0,
+ * offsets[B] = N.  Memory grows with N, never with B times the longest sequence.  The entries keep no state.  A sequence's
+ * results depend on its own frames only: they are bit-identical alone, anywhere in a batch and next to any neighbours.
+ * egoego_amass_last_error() describes the last failure of an egoego_amass_* call.
+ * ================================================================================================================== */
+const char* egoego_amass_last_error(void);
+/* The longest sequence egoego_amass_floor_contacts accepts (65536 raw frames). */
+int egoego_amass_max_frames(void);
+/* The first 22 joints of the body model at zero betas for N frames: d_root_orient [N][3], d_pose_body [N][63], d_trans [N][3]
+ * (the poses already rounded to fp32), d_j_template [22][3] (the model's rest joints); parents_host: 22 ints on the host,
+ * parents[j] < j for j >= 1 -> d_joints [N][22][3] (chain + trans) and d_head_rot [N][9], the global rotation of joint 15,
+ * row-major.  fp64 inside, rounded once. */
+int egoego_amass_joints(const float* d_root_orient, const float* d_pose_body, const float* d_trans, const float* d_j_template,
+                        const int32_t* parents_host, int n_frames, float* d_joints, float* d_head_rot, void* stream);
+/* Bytes of workspace egoego_amass_floor_contacts needs for B sequences of n_frames frames in all (0 = bad shape). */
+size_t egoego_amass_floor_workspace_bytes(int n_frames, int B);
+/* determine_floor_height_and_contacts (:160-338) for B packed sequences d_joints [N][22][3] (z up) at their own frame rates:
+ * d_size_thresh [B] int32 holds int(0.25 * fps) per sequence.  offsets_host: B + 1 ints on the host, validated (every sequence
+ * 1..egoego_amass_max_frames() frames); d_offsets: the same values on the device.  Outputs as egoego_eval_floor_contacts, packed:
+ * d_floor_height, d_offset_floor_height, d_discard, d_n_static, d_n_groups [B]; d_contacts [N][22]; d_labels (optional) int32
+ * [2 N], sequence b's 2 L entries from 2 * offsets[b].  A sequence of at most egoego_eval_max_frames() frames runs in LDS, a
+ * longer one (and every one when force_long != 0) in its slice of the workspace, with the same arithmetic and the same bits.
+ * The workspace (256-byte aligned) may hold any bytes on entry.  One workgroup per sequence. */
+int egoego_amass_floor_contacts(const float* d_joints, const int32_t* offsets_host, const int32_t* d_offsets, const int32_t* d_size_thresh,
+                                int B, int force_long, float* d_floor_height, float* d_offset_floor_height, float* d_contacts,
+                                int32_t* d_discard, int32_t* d_labels, int32_t* d_n_static, int32_t* d_n_groups, void* workspace,
+                                size_t workspace_bytes, void* stream);
+/* The saved tracks (:443-472) for n_out output frames: output frame i of sequence d_seq[i] is raw frame d_src[i] (the downsample
+ * table plus the sequence's first row); d_out_offsets [B + 1] delimits each sequence's output frames.  d_joints_out [n_out][22][3]
+ * (z minus d_offset_floor_height[b]), d_contacts_out [n_out][22] fp64, d_head_trans [n_out][3], d_rot6d [n_out][6], d_qpos
+ * [n_out][7] (position, then w, x, y, z with w >= 0), d_rot6d_diff [n_out][6] and d_trans_diff [n_out][3] (frame t + 1 against t;
+ * zero in a sequence's last row), d_vels [n_out][6] (get_head_vel :111-137; the last row repeats the one before), d_same [n_out]
+ * uint8: 1 where the pair took the |1 -+ q0| < 1e-6 branch.  fp64 from the fp32 inputs, rounded once. */
+int egoego_amass_head(const float* d_joints, const float* d_head_rot, const float* d_contacts, const float* d_offset_floor_height,
+                      const int32_t* d_src, const int32_t* d_seq, const int32_t* d_out_offsets, int n_out, int n_frames, int B,
+                      float* d_joints_out, double* d_contacts_out, float* d_head_trans, float* d_rot6d, float* d_qpos, float* d_rot6d_diff,
+                      float* d_trans_diff, float* d_vels, uint8_t* d_same, void* stream);
 
 #ifdef __cplusplus
 }
