@@ -7,27 +7,24 @@
 //                        rounded once to fp32.  No joint below 22 has an ancestor at or beyond 22, so the hands' pose and the
 //                        6890 vertices the reference computes on the way never reach Jtr[:, :22].
 //   amass_floor_kernel   determine_floor_height_and_contacts (:160-338) at the raw frame rate, one 1024-thread workgroup per
-//                        sequence, the algorithm and the tie rules of eval_floor_kernel (eval_metrics.h, steps 1-7 there).  A
-//                        sequence of at most evalm::MAX_T frames keeps its arrays in LDS with a 12-bit frame field; a longer one
-//                        (up to MAX_LEN frames) keeps them in its slice of the caller's workspace with a 32-bit frame and a 32-bit
-//                        compacted index.  Both are the same function body (floor_body<LONG>): only where the arrays live and how
-//                        wide a sample's key is differ, so a sequence gives the same bits on either path.  Still one workgroup per
-//                        sequence: every hand-off is a __syncthreads(); no workgroup reads what another wrote.
+//                        sequence: floor_common.h's floor_body<LONG> (steps 1-7 there), which eval_floor_kernel (eval_metrics.h)
+//                        runs too.  A sequence of at most evalm::MAX_T frames keeps its arrays in LDS with a 12-bit frame field;
+//                        a longer one (up to MAX_LEN frames) keeps them in its slice of the caller's workspace with a 32-bit
+//                        frame and a 32-bit compacted index, and gives the same bits.  Still one workgroup per sequence: every
+//                        hand-off is a __syncthreads(); no workgroup reads what another wrote.
 //   amass_head_kernel    one fp64 thread per output frame: the gather through the downsample table, the floor shift, and the head
 //                        tracks (:454-472 with get_head_vel :111-137).
 #pragma once
 #include "floor_common.h"
+#include "quat_f64.h"
 
 namespace amass {
 
 using evalm::NJ;
 using evalm::HEAD;
-using evalm::contact_joint;
-using evalm::within_eps;
+using evalm::MAX_LEN;
 
-static constexpr int MAX_LEN = 1 << 16;  // frames per sequence: 2 * MAX_LEN samples, 128 per thread in a scan
 static constexpr int THREADS = evalm::FC_THREADS;
-static constexpr int SCAN_WORDS = 2 * MAX_LEN / THREADS / 32;  // flag words a thread keeps across a scan
 static constexpr int WS_BYTES_PER_ELEM = 8 + 4 * 6 + 1;        // sp (8), sh, lab, gmed, gsz, rootv, mask (4 each), vf (1)
 
 // workspace elements: sequence b's slice of every array starts at element 4 * offsets[b] + 2 * b and holds 4 L + 2 of them
@@ -45,23 +42,6 @@ struct JointArgs {
     int parents[NJ];
     int N;
 };
-
-// Rodrigues with the factors from their series below |a|^2 = 1e-12
-EG_D void rodrigues(double x, double y, double z, double (&R)[9]) {
-    const double a2 = x * x + y * y + z * z;
-    double s, c;
-    if (a2 < 1e-12) {
-        s = 1.0 - a2 / 6.0;
-        c = 0.5 - a2 / 24.0;
-    } else {
-        const double a = sqrt(a2), h = sin(0.5 * a);
-        s = sin(a) / a;
-        c = 2.0 * h * h / a2;
-    }
-    R[0] = 1.0 - c * (y * y + z * z); R[1] = c * x * y - s * z;         R[2] = c * x * z + s * y;
-    R[3] = c * x * y + s * z;         R[4] = 1.0 - c * (x * x + z * z); R[5] = c * y * z - s * x;
-    R[6] = c * x * z - s * y;         R[7] = c * y * z + s * x;         R[8] = 1.0 - c * (x * x + y * y);
-}
 
 __global__ void amass_joints_kernel(JointArgs a) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -110,314 +90,23 @@ struct FloorArgs {
     int B, N, cap, force_long;  // cap: power of two >= 64, the LDS layout evalm::floor_lds(cap) of the short path
 };
 
-// A sample's sort key: (compacted index, frame)
-template <bool LONG>
-struct Key;
-template <>
-struct Key<false> {
-    typedef uint32_t T;
-    static constexpr int SHIFT = evalm::FRAME_BITS;
-};
-template <>
-struct Key<true> {
-    typedef unsigned long long T;
-    static constexpr int SHIFT = 32;
-};
-
-// evalm::block_scan for up to 32 * SCAN_WORDS entries per thread
-template <typename F, typename E>
-EG_D int block_scan(int n, int* part, F flag, E emit) {
-    const int tid = threadIdx.x, chunk = (n + THREADS - 1) / THREADS;
-    const int lo = min(tid * chunk, n), hi = min(lo + chunk, n);
-    uint32_t bits[SCAN_WORDS];
-    int cnt = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_WORDS; ++w) {
-        bits[w] = 0;
-        const int s = lo + 32 * w, e = min(s + 32, hi);
-        for (int i = s; i < e; ++i) bits[w] |= (flag(i) ? 1u : 0u) << (i - s);
-        cnt += __popc(bits[w]);
-    }
-    part[tid] = cnt;
-    __syncthreads();
-    for (int d = 1; d < THREADS; d <<= 1) {
-        const int v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int pre = part[tid] - cnt;
-    const int total = part[THREADS - 1];
-#pragma unroll
-    for (int w = 0; w < SCAN_WORDS; ++w) {
-        const int s = lo + 32 * w, e = min(s + 32, hi);
-        for (int i = s; i < e; ++i) {
-            const bool f = (bits[w] >> (i - s)) & 1u;
-            emit(i, pre, f);
-            pre += f;
-        }
-    }
-    __syncthreads();
-    return total;
-}
-
-// the arrays of one sequence, in LDS or in its slice of the workspace
-template <bool LONG>
-struct FloorMem {
-    float* sh;
-    typename Key<LONG>::T* sp;
-    int* lab;
-    float* gmed;
-    int* gsz;
-    float* rootv;
-    uint32_t* mask;
-    uint8_t* vf;
-};
-
-// the median (fp32, numpy's) of the root heights of the unique frames of the samples labelled `label`
-template <bool LONG>
-EG_D float root_median(int label, int n, int L, const float* P, const FloorMem<LONG>& m, int* part, float* s_pair) {
-    typedef typename Key<LONG>::T K;
-    const int tid = threadIdx.x;
-    for (int w = tid; w < (L + 31) / 32; w += THREADS) m.mask[w] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += THREADS)
-        if (m.lab[i] == label) {
-            const uint32_t f = (uint32_t)(m.sp[i] & (((K)1 << Key<LONG>::SHIFT) - 1));
-            atomicOr(&m.mask[f >> 5], 1u << (f & 31));
-        }
-    __syncthreads();
-    const int cnt = block_scan(L, part, [&](int t) { return (m.mask[t >> 5] >> (t & 31)) & 1u; },
-                               [&](int t, int pre, bool f) { if (f) m.rootv[pre] = P[(size_t)t * NJ * 3 + 2]; });
-    for (int i = tid; i < cnt; i += THREADS) {
-        const float v = m.rootv[i];
-        int r = 0;
-        for (int j = 0; j < cnt; ++j) {
-            const float u = m.rootv[j];
-            r += (u < v || (u == v && j < i)) ? 1 : 0;
-        }
-        if (r == (cnt - 1) / 2) s_pair[0] = v;
-        if (r == cnt / 2) s_pair[1] = v;
-    }
-    __syncthreads();
-    const float med = (s_pair[0] + s_pair[1]) * 0.5f;
-    __syncthreads();
-    return med;
-}
-
-// Steps 1-7 of eval_metrics.h for the L frames at P.  `b` is the sequence, `o0` its first frame.
-template <bool LONG>
-EG_D void floor_body(const FloorArgs& a, int b, int o0, int L, const FloorMem<LONG>& m, int* part, float* s_pair, unsigned long long* s_best) {
-    typedef typename Key<LONG>::T K;
-    constexpr int SHIFT = Key<LONG>::SHIFT;
-    const int tid = threadIdx.x;
-    const float* P = a.jpos + (size_t)o0 * NJ * 3;
-    float* const sh = m.sh;
-    K* const sp = m.sp;
-    int* const lab = m.lab;
-    float* const gmed = m.gmed;
-    int* const gsz = m.gsz;
-    uint8_t* const vf = m.vf;
-
-    // 1. velocity flags
-    for (int t = tid; t < L; t += THREADS) {
-        uint32_t flags = 0;
-        if (L >= 2) {
-            const int tv = t + 1 < L ? t : L - 2;
-            const float* p0 = P + (size_t)tv * NJ * 3;
-            const float* p1 = p0 + NJ * 3;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int j = contact_joint(k);
-                const double dx = (double)p1[3 * j] - (double)p0[3 * j], dy = (double)p1[3 * j + 1] - (double)p0[3 * j + 1],
-                             dz = (double)p1[3 * j + 2] - (double)p0[3 * j + 2];
-                if (sqrt(dx * dx + dy * dy + dz * dz) < evalm::VEL_THRESH) flags |= 1u << k;
-            }
-        }
-        vf[t] = (uint8_t)flags;
-    }
-    __syncthreads();
-
-    // 2. static toe heights, left frames then right frames
-    const int n = block_scan(2 * L, part, [&](int e) { return e < L ? (vf[e] & 1u) : ((vf[e - L] >> 1) & 1u); },
-                             [&](int e, int pre, bool f) {
-                                 if (!f) return;
-                                 const int fr = e < L ? e : e - L;
-                                 sh[pre] = P[(size_t)fr * NJ * 3 + 3 * (e < L ? 10 : 11) + 2];
-                                 sp[pre] = ((K)(uint32_t)pre << SHIFT) | (K)(uint32_t)fr;
-                             });
-
-    // 3. sort by (height, compacted index)
-    int np2 = 2;
-    while (np2 < n) np2 <<= 1;
-    for (int i = n + tid; i < np2; i += THREADS) {
-        sh[i] = __builtin_inff();
-        sp[i] = ~(K)0;
-    }
-    __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const float hi_ = sh[i], hl = sh[l];
-                    const K pi = sp[i], pl = sp[l];
-                    const bool gt = hi_ > hl || (hi_ == hl && pi > pl);
-                    if (gt == ((i & k) == 0)) {
-                        sh[i] = hl; sh[l] = hi_;
-                        sp[i] = pl; sp[l] = pi;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-
-    // 4. DBSCAN on the sorted line
-    auto is_core = [&](int i) {
-        const bool l1 = i >= 1 && within_eps(sh[i], sh[i - 1]), r1 = i + 1 < n && within_eps(sh[i], sh[i + 1]);
-        return (l1 && r1) || (i >= 2 && within_eps(sh[i], sh[i - 2])) || (i + 2 < n && within_eps(sh[i], sh[i + 2]));
-    };
-    for (int i = tid; i < n; i += THREADS) lab[i] = is_core(i) ? 1 : 0;
-    __syncthreads();
-    // raw cluster ids, left to right: lab[i] = id for a core, -1 otherwise
-    const int Kc = block_scan(n, part, [&](int i) { return lab[i] && !(i >= 1 && lab[i - 1] && within_eps(sh[i], sh[i - 1])); },
-                              [&](int i, int pre, bool f) {
-                                  // (lab[i] is read by the owner of i and of i + 1 only, both before any emit: block_scan)
-                                  lab[i] = lab[i] ? pre + (f ? 1 : 0) - 1 : -1;
-                              });
-    for (int k = tid; k < Kc; k += THREADS) gsz[k] = 0x7fffffff;
-    __syncthreads();
-    for (int i = tid; i < n; i += THREADS)
-        if (lab[i] >= 0) atomicMin(&gsz[lab[i]], (int)(uint32_t)(sp[i] >> SHIFT));
-    __syncthreads();
-    {  // a cluster's number = how many clusters appear before it in input order; the ranks wait in gmed (free until step 5)
-        int* rank = (int*)gmed;
-        for (int k = tid; k < Kc; k += THREADS) {
-            const int mine = gsz[k];
-            int r = 0;
-            for (int o = 0; o < Kc; ++o) r += gsz[o] < mine ? 1 : 0;
-            rank[k] = r;
-        }
-        __syncthreads();
-        for (int k = tid; k < Kc; k += THREADS) gsz[k] = rank[k];
-        __syncthreads();
-    }
-    // A border point takes the lower-numbered of the (at most two) neighbouring cores within eps.  First the non-core points
-    // only, stored as -(label + 2) so that an entry's sign, all a neighbour looks at, does not change; then every entry decodes.
-    for (int i = tid; i < n; i += THREADS) {
-        if (lab[i] >= 0) continue;
-        const int cl = i >= 1 && lab[i - 1] >= 0 && within_eps(sh[i], sh[i - 1]) ? gsz[lab[i - 1]] : -1;
-        const int cr = i + 1 < n && lab[i + 1] >= 0 && within_eps(sh[i], sh[i + 1]) ? gsz[lab[i + 1]] : -1;
-        const int fin = cl < 0 ? cr : (cr < 0 ? cl : min(cl, cr));
-        if (fin >= 0) lab[i] = -(fin + 2);
-    }
-    __syncthreads();
-    int* const labels = a.labels ? a.labels + 2 * (size_t)o0 : nullptr;
-    for (int i = tid; i < n; i += THREADS) {
-        const int v = lab[i];
-        const int fin = v >= 0 ? gsz[v] : -v - 2;  // (-1 stays -1)
-        lab[i] = fin;
-        if (labels) labels[(uint32_t)(sp[i] >> SHIFT)] = fin;
-    }
-    if (labels)
-        for (int i = n + tid; i < 2 * L; i += THREADS) labels[i] = -2;
-    __syncthreads();
-
-    // 5. group medians; slot g = label + 1 (slot 0: noise)
-    for (int i = tid; i < n; i += THREADS) {
-        const int l = lab[i];
-        if (l < 0) continue;
-        if (i == 0 || lab[i - 1] != l) gsz[l + 1] = i;
-        if (i == n - 1 || lab[i + 1] != l) ((int*)gmed)[l + 1] = i;
-    }
-    __syncthreads();
-    for (int g = 1 + tid; g <= Kc; g += THREADS) {
-        const int s = gsz[g], c = ((int*)gmed)[g] - s + 1;
-        gmed[g] = (sh[s + (c - 1) / 2] + sh[s + c / 2]) * 0.5f;
-        gsz[g] = c;
-    }
-    const int nn = block_scan(n, part, [&](int i) { return lab[i] < 0; }, [&](int, int, bool) {});
-    block_scan(n, part, [&](int i) { return lab[i] < 0; },
-               [&](int i, int pre, bool f) {
-                   if (!f) return;
-                   if (pre == (nn - 1) / 2) s_pair[0] = sh[i];
-                   if (pre == nn / 2) s_pair[1] = sh[i];
-               });
-    if (tid == 0) {
-        gsz[0] = nn;
-        gmed[0] = nn ? (s_pair[0] + s_pair[1]) * 0.5f : __builtin_inff();
-        *s_best = ~0ull;
-    }
-    __syncthreads();
-
-    float floor_h = 0.f;
-    int discard = 0;
-    if (n > 0) {
-        for (int g = tid; g <= Kc; g += THREADS)
-            if (gsz[g] > 0) {
-                uint32_t u = __float_as_uint(gmed[g]);
-                u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // order-preserving
-                atomicMin(s_best, ((unsigned long long)u << 32) | (uint32_t)g);
-            }
-        __syncthreads();
-        const int gbest = (int)(*s_best & 0xffffffffu);
-        floor_h = gmed[gbest];
-        // 6. DISCARD_TERRAIN_SEQUENCES (:267-277)
-        const int size_thresh = a.size_thresh[b];
-        const float min_root = root_median<LONG>(gbest - 1, n, L, P, m, part, s_pair);
-        for (int g = 0; g <= Kc && !discard; ++g) {
-            if (gsz[g] == 0 || !(gmed[g] > floor_h + evalm::TERRAIN_H) || !(gsz[g] > size_thresh)) continue;
-            const float rm = root_median<LONG>(g - 1, n, L, P, m, part, s_pair);
-            if (rm > min_root + evalm::ROOT_H) discard = 1;
-        }
-    }
-    if (tid == 0) {
-        a.floor_h[b] = floor_h;
-        a.offset_h[b] = n > 0 ? floor_h - evalm::FLOOR_OFFSET : 0.f;
-        a.discard[b] = discard;
-        a.n_static[b] = n;
-        a.n_groups[b] = Kc + (nn > 0 ? 1 : 0);
-    }
-
-    // 7. contacts
-    float* C = a.contacts + (size_t)o0 * NJ;
-    for (int t = tid; t < L; t += THREADS) {
-        uint32_t on = 0;
-        const uint32_t flags = vf[t];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int j = contact_joint(k);
-            const float hgt = P[(size_t)t * NJ * 3 + 3 * j + 2] - floor_h;
-            if (((flags >> k) & 1u) && hgt < (k < 2 ? evalm::TOE_H : evalm::ANKLE_H)) on |= 1u << j;
-        }
-        for (int j = 0; j < NJ; ++j) C[(size_t)t * NJ + j] = (float)((on >> j) & 1u);
-    }
-}
-
+// floor_common.h's floor_body on packed sequences: sequence b owns the frames offsets[b] .. offsets[b + 1] and writes its L rows
 __global__ void __launch_bounds__(THREADS) amass_floor_kernel(FloorArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fc_lds[];
     __shared__ float s_pair[2];
     __shared__ unsigned long long s_best;
-    int* part = (int*)(fc_lds + evalm::floor_lds(a.cap).part);
     const int b = blockIdx.x;
     // whatever the offsets hold, a sequence stays inside the N frames and inside its slice of the workspace
     const int o0 = min(max(a.offsets[b], 0), a.N);
     const int L = min(min(max(a.offsets[b + 1], o0), a.N) - o0, MAX_LEN);
+    const evalm::FloorSeq q{a.jpos + (size_t)o0 * NJ * 3, L, a.size_thresh[b], a.contacts + (size_t)o0 * NJ, L,
+                            a.labels ? a.labels + 2 * (size_t)o0 : nullptr, 2 * L,
+                            a.floor_h + b, a.offset_h + b, a.discard + b, a.n_static + b, a.n_groups + b};
     if (!a.force_long && 2 * L <= a.cap && L <= evalm::MAX_T) {
-        const evalm::FloorLds lay = evalm::floor_lds(a.cap);
-        FloorMem<false> m;
-        m.sh = (float*)(fc_lds + lay.sh);
-        m.sp = (uint32_t*)(fc_lds + lay.sp);
-        m.lab = (int*)(fc_lds + lay.lab);
-        m.gmed = (float*)(fc_lds + lay.gmed);
-        m.gsz = (int*)(fc_lds + lay.gsz);
-        m.rootv = (float*)(fc_lds + lay.rootv);
-        m.mask = (uint32_t*)(fc_lds + lay.mask);
-        m.vf = fc_lds + lay.vf;
-        floor_body<false>(a, b, o0, L, m, part, s_pair, &s_best);
+        evalm::floor_body<false>(q, evalm::floor_mem_lds(fc_lds, a.cap), s_pair, &s_best);
     } else {
         const size_t E = ws_elems(a.N, a.B), e0 = 4 * (size_t)o0 + 2 * (size_t)b;
-        FloorMem<true> m;
+        evalm::FloorMem<true> m;
         m.sp = (unsigned long long*)a.ws + e0;
         unsigned char* p = a.ws + 8 * E;
         m.sh = (float*)p + e0;             p += 4 * E;
@@ -427,7 +116,8 @@ __global__ void __launch_bounds__(THREADS) amass_floor_kernel(FloorArgs a) {
         m.rootv = (float*)p + e0;          p += 4 * E;
         m.mask = (uint32_t*)p + e0;        p += 4 * E;
         m.vf = p + e0;
-        floor_body<true>(a, b, o0, L, m, part, s_pair, &s_best);
+        m.part = (int*)(fc_lds + evalm::floor_lds(a.cap).part);
+        evalm::floor_body<true>(q, m, s_pair, &s_best);
     }
 }
 

@@ -57,8 +57,7 @@ int egoego_amass_floor_contacts(const float* d_joints, const int32_t* offsets_ho
     }
     const int N = offsets_host[B];
     if (int rc = check_workspace(workspace, workspace_bytes, egoego_amass_floor_workspace_bytes(N, B))) return rc;
-    int cap = 64;
-    while (cap < 2 * longest_short) cap <<= 1;
+    const int cap = evalm::floor_cap(longest_short);
     const size_t lds = evalm::floor_lds(cap).total;
     FloorArgs a{d_joints, d_offsets, d_size_thresh, d_floor_height, d_offset_floor_height, d_contacts, d_discard, d_labels, d_n_static,
                 d_n_groups, (unsigned char*)workspace, B, N, cap, force_long ? 1 : 0};

@@ -24,6 +24,7 @@
 // tile, chunk or position its frame falls in, and the rows of an MFMA do not interact.
 #pragma once
 #include "common.h"
+#include "quat_f64.h"
 
 namespace bodym {
 
@@ -56,23 +57,6 @@ struct FrameArgs {
     float* joints;        // [F][52][3]
     int F, S, K16;
 };
-
-// R = I + (sin a / a) K + ((1 - cos a) / a^2) K^2, a = |v|; the two factors from their series below 1e-6 (exact at v = 0)
-EG_D void rodrigues(double x, double y, double z, double R[9]) {
-    const double a2 = x * x + y * y + z * z;
-    double s, c;
-    if (a2 < 1e-12) {
-        s = 1.0 - a2 / 6.0;
-        c = 0.5 - a2 / 24.0;
-    } else {
-        const double a = sqrt(a2), h = sin(0.5 * a);
-        s = sin(a) / a;
-        c = 2.0 * h * h / a2;
-    }
-    R[0] = 1.0 - c * (y * y + z * z); R[1] = c * x * y - s * z;         R[2] = c * x * z + s * y;
-    R[3] = c * x * y + s * z;         R[4] = 1.0 - c * (x * x + z * z); R[5] = c * y * z - s * x;
-    R[6] = c * x * z - s * y;         R[7] = c * y * z + s * x;         R[8] = 1.0 - c * (x * x + y * y);
-}
 
 __global__ void body_frame_kernel(FrameArgs a) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;

@@ -10,27 +10,8 @@
 //                        t, t + 256, ... and the partial sums meet in a fixed shuffle / LDS order, so a sample's numbers depend
 //                        on its own frames and length only: not on the batch, its position in it or the padded T.
 //
-// The floor kernel, step by step (n = number of static toe samples, at most 2 L):
-//   1. per frame, eight velocity flags (|p[t + 1] - p[t]| < 0.005 in fp64; the last frame repeats the one before it);
-//   2. one block scan over the 2 L virtual entries (left toe frames, then right toe frames) compacts the static heights in the
-//      reference's order; a sample carries (compacted index << 12 | frame);
-//   3. bitonic sort by (height, compacted index) over the next power of two;
-//   4. DBSCAN(eps = 0.005, min_samples = 3) on the sorted line.  A point is core when three points, itself included, lie within
-//      eps: h[i + 2] - h[i] <= eps, or h[i] - h[i - 2] <= eps, or both neighbours within eps.  Two cores within eps of each other
-//      have only cores between them (any point between them sees both), so a core opens a cluster exactly when its left
-//      neighbour is not a core within eps: one more scan numbers the clusters left to right.  sklearn numbers them by first
-//      appearance in input order, i.e. by the smallest compacted index among their cores: an LDS atomic min per cluster and a
-//      rank count give that order.  A non-core point within eps of a core is a border point; only its two sorted neighbours can
-//      be such cores (a core two places away would make the point itself core), and it takes the lower-numbered cluster if both
-//      are.  With min_samples = 3 that last case cannot arise (the point would see both cores and be core); the rule is kept
-//      as stated.  Everything else is noise (-1).  Clusters are contiguous runs of the sorted line; the noise group is not.
-//   5. group medians in fp32 ((a + b) * 0.5f of the two middle samples, numpy's mean of two): runs by position, noise by a scan;
-//      floor = the smallest, the first group in label order (-1, 0, 1, ...) on a tie;
-//   6. the discard test needs a group's median root height over its unique frames: a frame bit mask (LDS atomic or), a scan to
-//      gather the root heights, and a rank count for the middle ones.  It runs for the floor group and for the groups that pass
-//      the two cheap tests (median height, size) only;
-//   7. contacts from the velocity flags and the heights above floor_height (not the offset height).
-// The thresholds, the contact joints and the LDS layout live in floor_common.h, which amass_prep.h's floor kernel shares.
+// The floor kernel's seven steps, its thresholds, the contact joints and the LDS layout live in floor_common.h, which
+// amass_prep.h's floor kernel shares.
 #pragma once
 #include "common.h"
 #include "quat_f64.h"
@@ -137,274 +118,18 @@ struct FloorArgs {
     int B, T, size_thresh, cap;  // cap: power of two >= max(2 T, 64), fixes the LDS layout
 };
 
-// Exclusive prefix sum of flag(i), i < n, over the block: emit(i, prefix, flag(i)) for every i, returns the total.  A thread owns
-// a contiguous run of ceil(n / threads) <= 32 entries and evaluates each flag once, before any emit runs.
-template <typename F, typename E>
-EG_D int block_scan(int n, int* part, F flag, E emit) {
-    const int tid = threadIdx.x, chunk = (n + FC_THREADS - 1) / FC_THREADS;
-    const int lo = min(tid * chunk, n), hi = min(lo + chunk, n);
-    uint32_t bits = 0;
-    for (int i = lo; i < hi; ++i) bits |= (flag(i) ? 1u : 0u) << (i - lo);
-    const int cnt = __popc(bits);
-    part[tid] = cnt;
-    __syncthreads();
-    for (int d = 1; d < FC_THREADS; d <<= 1) {
-        const int v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int pre = part[tid] - cnt;
-    const int total = part[FC_THREADS - 1];
-    for (int i = lo; i < hi; ++i) {
-        const bool f = (bits >> (i - lo)) & 1u;
-        emit(i, pre, f);
-        pre += f;
-    }
-    __syncthreads();
-    return total;
-}
-
-// the median (fp32, numpy's) of the root heights of the unique frames of the samples labelled `label`
-EG_D float root_median(int label, int n, int L, const float* P, const uint32_t* sp, const int* lab, uint32_t* mask, float* rootv, int* part,
-                       float* s_pair) {
-    const int tid = threadIdx.x;
-    for (int w = tid; w < (L + 31) / 32; w += FC_THREADS) mask[w] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += FC_THREADS)
-        if (lab[i] == label) {
-            const uint32_t f = sp[i] & (MAX_T - 1);
-            atomicOr(&mask[f >> 5], 1u << (f & 31));
-        }
-    __syncthreads();
-    const int m = block_scan(L, part, [&](int t) { return (mask[t >> 5] >> (t & 31)) & 1u; },
-                             [&](int t, int pre, bool f) { if (f) rootv[pre] = P[(size_t)t * NJ * 3 + 2]; });
-    for (int i = tid; i < m; i += FC_THREADS) {
-        const float v = rootv[i];
-        int r = 0;
-        for (int j = 0; j < m; ++j) {
-            const float u = rootv[j];
-            r += (u < v || (u == v && j < i)) ? 1 : 0;
-        }
-        if (r == (m - 1) / 2) s_pair[0] = v;
-        if (r == m / 2) s_pair[1] = v;
-    }
-    __syncthreads();
-    const float med = (s_pair[0] + s_pair[1]) * 0.5f;
-    __syncthreads();
-    return med;
-}
-
+// floor_common.h's floor_body on a padded batch: sequence b owns rows b T .. b T + lengths[b], every output is written for all T
 __global__ void __launch_bounds__(FC_THREADS) eval_floor_kernel(FloorArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fc_lds[];
     __shared__ float s_pair[2];
     __shared__ unsigned long long s_best;
-    const FloorLds lay = floor_lds(a.cap);
-    float* sh = (float*)(fc_lds + lay.sh);
-    uint32_t* sp = (uint32_t*)(fc_lds + lay.sp);
-    int* lab = (int*)(fc_lds + lay.lab);
-    float* gmed = (float*)(fc_lds + lay.gmed);
-    int* gsz = (int*)(fc_lds + lay.gsz);
-    float* rootv = (float*)(fc_lds + lay.rootv);
-    uint8_t* vf = fc_lds + lay.vf;
-    uint32_t* mask = (uint32_t*)(fc_lds + lay.mask);
-    int* part = (int*)(fc_lds + lay.part);
-
-    const int tid = threadIdx.x, b = blockIdx.x, T = a.T;
+    const int b = blockIdx.x, T = a.T;
     int L = a.lengths ? a.lengths[b] : T;
     L = L < 0 ? 0 : (L > T ? T : L);
-    const float* P = a.jpos + (size_t)b * T * NJ * 3;
-
-    // 1. velocity flags
-    for (int t = tid; t < L; t += FC_THREADS) {
-        uint32_t flags = 0;
-        if (L >= 2) {
-            const int tv = t + 1 < L ? t : L - 2;
-            const float* p0 = P + (size_t)tv * NJ * 3;
-            const float* p1 = p0 + NJ * 3;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int j = contact_joint(k);
-                const double dx = (double)p1[3 * j] - (double)p0[3 * j], dy = (double)p1[3 * j + 1] - (double)p0[3 * j + 1],
-                             dz = (double)p1[3 * j + 2] - (double)p0[3 * j + 2];
-                if (sqrt(dx * dx + dy * dy + dz * dz) < VEL_THRESH) flags |= 1u << k;
-            }
-        }
-        vf[t] = (uint8_t)flags;
-    }
-    __syncthreads();
-
-    // 2. static toe heights, left frames then right frames
-    const int n = block_scan(2 * L, part, [&](int e) { return e < L ? (vf[e] & 1u) : ((vf[e - L] >> 1) & 1u); },
-                             [&](int e, int pre, bool f) {
-                                 if (!f) return;
-                                 const int fr = e < L ? e : e - L;
-                                 sh[pre] = P[(size_t)fr * NJ * 3 + 3 * (e < L ? 10 : 11) + 2];
-                                 sp[pre] = ((uint32_t)pre << FRAME_BITS) | (uint32_t)fr;
-                             });
-
-    // 3. sort by (height, compacted index)
-    int np2 = 2;
-    while (np2 < n) np2 <<= 1;
-    for (int i = n + tid; i < np2; i += FC_THREADS) {
-        sh[i] = __builtin_inff();
-        sp[i] = 0xffffffffu;
-    }
-    __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += FC_THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const float hi_ = sh[i], hl = sh[l];
-                    const uint32_t pi = sp[i], pl = sp[l];
-                    const bool gt = hi_ > hl || (hi_ == hl && pi > pl);
-                    if (gt == ((i & k) == 0)) {
-                        sh[i] = hl; sh[l] = hi_;
-                        sp[i] = pl; sp[l] = pi;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-
-    // 4. DBSCAN on the sorted line
-    auto is_core = [&](int i) {
-        const bool l1 = i >= 1 && within_eps(sh[i], sh[i - 1]), r1 = i + 1 < n && within_eps(sh[i], sh[i + 1]);
-        return (l1 && r1) || (i >= 2 && within_eps(sh[i], sh[i - 2])) || (i + 2 < n && within_eps(sh[i], sh[i + 2]));
-    };
-    for (int i = tid; i < n; i += FC_THREADS) lab[i] = is_core(i) ? 1 : 0;
-    __syncthreads();
-    // raw cluster ids, left to right: lab[i] = id for a core, -1 otherwise
-    const int K = block_scan(n, part, [&](int i) { return lab[i] && !(i >= 1 && lab[i - 1] && within_eps(sh[i], sh[i - 1])); },
-                             [&](int i, int pre, bool f) {
-                                 // (lab[i] is read by the owner of i and of i + 1 only, both before any emit: block_scan)
-                                 lab[i] = lab[i] ? pre + (f ? 1 : 0) - 1 : -1;
-                             });
-    for (int k = tid; k < K; k += FC_THREADS) gsz[k] = 0x7fffffff;
-    __syncthreads();
-    for (int i = tid; i < n; i += FC_THREADS)
-        if (lab[i] >= 0) atomicMin(&gsz[lab[i]], (int)(sp[i] >> FRAME_BITS));
-    __syncthreads();
-    {  // a cluster's number = how many clusters appear before it in input order; K <= n / 3 < 3 * FC_THREADS
-        int rank[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int k = tid + q * FC_THREADS;
-            rank[q] = 0;
-            if (k < K) {
-                const int mine = gsz[k];
-                for (int o = 0; o < K; ++o) rank[q] += gsz[o] < mine ? 1 : 0;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int k = tid + q * FC_THREADS;
-            if (k < K) gsz[k] = rank[q];
-        }
-        __syncthreads();
-    }
-    {
-        int fin[FC_ELEMS];
-#pragma unroll
-        for (int q = 0; q < FC_ELEMS; ++q) {
-            const int i = tid + q * FC_THREADS;
-            fin[q] = -1;
-            if (i < n) {
-                if (lab[i] >= 0) {
-                    fin[q] = gsz[lab[i]];
-                } else {
-                    const int cl = i >= 1 && lab[i - 1] >= 0 && within_eps(sh[i], sh[i - 1]) ? gsz[lab[i - 1]] : -1;
-                    const int cr = i + 1 < n && lab[i + 1] >= 0 && within_eps(sh[i], sh[i + 1]) ? gsz[lab[i + 1]] : -1;
-                    fin[q] = cl < 0 ? cr : (cr < 0 ? cl : min(cl, cr));
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < FC_ELEMS; ++q) {
-            const int i = tid + q * FC_THREADS;
-            if (i < n) {
-                lab[i] = fin[q];
-                if (a.labels) a.labels[(size_t)b * 2 * T + (sp[i] >> FRAME_BITS)] = fin[q];
-            }
-        }
-        if (a.labels)
-            for (int i = n + tid; i < 2 * T; i += FC_THREADS) a.labels[(size_t)b * 2 * T + i] = -2;
-        __syncthreads();
-    }
-
-    // 5. group medians; slot g = label + 1 (slot 0: noise)
-    for (int i = tid; i < n; i += FC_THREADS) {
-        const int l = lab[i];
-        if (l < 0) continue;
-        if (i == 0 || lab[i - 1] != l) gsz[l + 1] = i;
-        if (i == n - 1 || lab[i + 1] != l) ((int*)gmed)[l + 1] = i;
-    }
-    __syncthreads();
-    for (int g = 1 + tid; g <= K; g += FC_THREADS) {
-        const int s = gsz[g], m = ((int*)gmed)[g] - s + 1;
-        gmed[g] = (sh[s + (m - 1) / 2] + sh[s + m / 2]) * 0.5f;
-        gsz[g] = m;
-    }
-    const int nn = block_scan(n, part, [&](int i) { return lab[i] < 0; }, [&](int, int, bool) {});
-    block_scan(n, part, [&](int i) { return lab[i] < 0; },
-               [&](int i, int pre, bool f) {
-                   if (!f) return;
-                   if (pre == (nn - 1) / 2) s_pair[0] = sh[i];
-                   if (pre == nn / 2) s_pair[1] = sh[i];
-               });
-    if (tid == 0) {
-        gsz[0] = nn;
-        gmed[0] = nn ? (s_pair[0] + s_pair[1]) * 0.5f : __builtin_inff();
-        s_best = ~0ull;
-    }
-    __syncthreads();
-
-    float floor_h = 0.f;
-    int discard = 0;
-    if (n > 0) {
-        for (int g = tid; g <= K; g += FC_THREADS)
-            if (gsz[g] > 0) {
-                uint32_t u = __float_as_uint(gmed[g]);
-                u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // order-preserving
-                atomicMin(&s_best, ((unsigned long long)u << 32) | (uint32_t)g);
-            }
-        __syncthreads();
-        const int gbest = (int)(s_best & 0xffffffffu);
-        floor_h = gmed[gbest];
-        // 6. DISCARD_TERRAIN_SEQUENCES (:267-277)
-        const float min_root = root_median(gbest - 1, n, L, P, sp, lab, mask, rootv, part, s_pair);
-        for (int g = 0; g <= K && !discard; ++g) {
-            if (gsz[g] == 0 || !(gmed[g] > floor_h + TERRAIN_H) || !(gsz[g] > a.size_thresh)) continue;
-            const float rm = root_median(g - 1, n, L, P, sp, lab, mask, rootv, part, s_pair);
-            if (rm > min_root + ROOT_H) discard = 1;
-        }
-    }
-    if (tid == 0) {
-        a.floor_h[b] = floor_h;
-        a.offset_h[b] = n > 0 ? floor_h - FLOOR_OFFSET : 0.f;
-        a.discard[b] = discard;
-        a.n_static[b] = n;
-        a.n_groups[b] = K + (nn > 0 ? 1 : 0);
-    }
-
-    // 7. contacts
-    float* C = a.contacts + (size_t)b * T * NJ;
-    for (int t = tid; t < T; t += FC_THREADS) {
-        uint32_t on = 0;
-        if (t < L) {
-            const uint32_t flags = vf[t];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int j = contact_joint(k);
-                const float hgt = P[(size_t)t * NJ * 3 + 3 * j + 2] - floor_h;
-                if (((flags >> k) & 1u) && hgt < (k < 2 ? TOE_H : ANKLE_H)) on |= 1u << j;
-            }
-        }
-        for (int j = 0; j < NJ; ++j) C[(size_t)t * NJ + j] = (float)((on >> j) & 1u);
-    }
+    const FloorSeq q{a.jpos + (size_t)b * T * NJ * 3, L, a.size_thresh, a.contacts + (size_t)b * T * NJ, T,
+                     a.labels ? a.labels + (size_t)b * 2 * T : nullptr, 2 * T,
+                     a.floor_h + b, a.offset_h + b, a.discard + b, a.n_static + b, a.n_groups + b};
+    floor_body<false>(q, floor_mem_lds(fc_lds, a.cap), s_pair, &s_best);
 }
 
 // ---------------------------------------------------------------- metrics

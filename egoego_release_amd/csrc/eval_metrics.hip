@@ -57,8 +57,7 @@ int egoego_eval_floor_contacts(const float* d_jpos, const int32_t* d_lengths, in
     if (int rc = check_bt(B, T)) return rc;
     if (T > MAX_T) return fail(EGOEGO_E_INVALID, "T = %d frames: at most %d per sequence (2 T samples must fit the LDS)", T, MAX_T);
     if (!(fps >= 0.f) || fps > 1e6f) return fail(EGOEGO_E_INVALID, "fps %g: 0..1e6 accepted", (double)fps);
-    int cap = 64;
-    while (cap < 2 * T) cap <<= 1;
+    const int cap = floor_cap(T);
     const size_t lds = floor_lds(cap).total;
     FloorArgs a{d_jpos, d_lengths, d_floor_height, d_offset_floor_height, d_contacts, d_discard, d_labels, d_n_static, d_n_groups,
                 B, T, (int)(0.25 * (double)fps), cap};

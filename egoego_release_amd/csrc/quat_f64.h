@@ -1,5 +1,6 @@
-// quat_f64.h — fp64 quaternions (w, x, y, z) for the kernels that compute in double and round once: the evaluation's forward
-// kinematics (eval_metrics.h) and the motion windows (motion_windows.h).  (The prefix kernel's Quat helpers in pointwise.h are fp32.)
+// quat_f64.h — fp64 rotations for the kernels that compute in double and round once: quaternions (w, x, y, z) for the
+// evaluation's forward kinematics (eval_metrics.h) and the motion windows (motion_windows.h), Rodrigues' matrix for the body
+// model (body_model.h) and the AMASS joints (amass_prep.h).  (The prefix kernel's Quat helpers in pointwise.h are fp32.)
 #pragma once
 #include "common.h"
 
@@ -31,4 +32,21 @@ EG_D void qd_rotate(QuatD q, const double (&p)[3], double (&o)[3]) {
     o[0] = p[0] + q.w * tx + (q.y * tz - q.z * ty);
     o[1] = p[1] + q.w * ty + (q.z * tx - q.x * tz);
     o[2] = p[2] + q.w * tz + (q.x * ty - q.y * tx);
+}
+
+// R = I + (sin a / a) K + ((1 - cos a) / a^2) K^2, a = |v|; the two factors from their series below 1e-6 (exact at v = 0)
+EG_D void rodrigues(double x, double y, double z, double (&R)[9]) {
+    const double a2 = x * x + y * y + z * z;
+    double s, c;
+    if (a2 < 1e-12) {
+        s = 1.0 - a2 / 6.0;
+        c = 0.5 - a2 / 24.0;
+    } else {
+        const double a = sqrt(a2), h = sin(0.5 * a);
+        s = sin(a) / a;
+        c = 2.0 * h * h / a2;
+    }
+    R[0] = 1.0 - c * (y * y + z * z); R[1] = c * x * y - s * z;         R[2] = c * x * z + s * y;
+    R[3] = c * x * y + s * z;         R[4] = 1.0 - c * (x * x + z * z); R[5] = c * y * z - s * x;
+    R[6] = c * x * z - s * y;         R[7] = c * y * z + s * x;         R[8] = 1.0 - c * (x * x + y * y);
 }

@@ -192,6 +192,35 @@ def test_forced_long_path_equals_the_evaluation_entry(long_cases):
             assert torch.equal(d["n_static"], det["n_static"]) and torch.equal(d["n_groups"], det["n_groups"]), force
 
 
+def test_ragged_lengths_equal_the_evaluation_entry():
+    """The sequences of eval_cases.batch() cut to different lengths (2, the shortest the evaluation entry takes; odd ones; the
+    full T): padded to T with `lengths` through the evaluation entry, packed end to end through this one, on both paths.  Per
+    sequence every output carries the same bits; the evaluation entry's rows past L are zero, its labels past n_static are -2,
+    and the padded frames hold 1e30, so that nothing past L can have been read."""
+    _, batch, _ = eval_cases.batch()
+    B, T = batch.shape[:2]
+    lengths = [T, 2, 17, T, 33, T - 1, 31]
+    assert len(lengths) == B
+    x_padded = np.full_like(batch, 1e30)
+    for b, L in enumerate(lengths):
+        x_padded[b, :L] = batch[b, :L]
+    off, contacts, discard, det = evaluate.determine_floor_height_and_contacts(dev(x_padded), eval_cases.FPS, lengths=lengths,
+                                                                               return_details=True)
+    assert int(det["n_static"][0]) == 0 and sum(int(n) > 0 for n in det["n_static"]) >= 4  # with and without static samples
+    offsets = np.concatenate([[0], np.cumsum(lengths)])
+    packed = dev(np.concatenate([batch[b, :L] for b, L in enumerate(lengths)]))
+    for force in (True, False):
+        d = details_of(packed, offsets, eval_cases.FPS, force_long=force)
+        assert torch.equal(d["offset"], off) and torch.equal(d["floor_height"], det["floor_height"]), force
+        assert torch.equal(d["discard"], discard), force
+        assert torch.equal(d["n_static"], det["n_static"]) and torch.equal(d["n_groups"], det["n_groups"]), force
+        for b, L in enumerate(lengths):
+            o, n = int(offsets[b]), int(det["n_static"][b])
+            assert torch.equal(d["contacts"][o:o + L], contacts[b, :L]) and not contacts[b, L:].any(), (force, b)
+            assert torch.equal(d["labels"][2 * o:2 * (o + L)], det["labels"][b, :2 * L]), (force, b)
+            assert n <= 2 * L and torch.all(det["labels"][b, n:] == -2), (force, b)
+
+
 # ------------------------------------------------------------------------------------------------ packing
 def pipeline(seqs, model, force_long=False):
     """seqs: [(root_orient, pose_body, trans, fps)] float32 arrays -> per sequence the tensors of the three stages."""
