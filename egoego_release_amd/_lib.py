@@ -90,7 +90,14 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_win_last_error", "egoego_win_max_window", "egoego_win_build", "egoego_win_stats_workspace_bytes", "egoego_win_stats",
            "egoego_win_motion",
            "egoego_amass_last_error", "egoego_amass_max_frames", "egoego_amass_joints", "egoego_amass_floor_workspace_bytes",
-           "egoego_amass_floor_contacts", "egoego_amass_head"]
+           "egoego_amass_floor_contacts", "egoego_amass_head",
+           "egoego_train_last_error", "egoego_train_ctx_create", "egoego_train_ctx_destroy", "egoego_train_workspace_bytes",
+           "egoego_train_saves_bytes", "egoego_train_forward", "egoego_train_backward", "egoego_train_dropout_mask", "egoego_train_saved"]
+LOSS_L1, LOSS_L2 = 0, 1
+TRAIN_SITE_ATTN, TRAIN_SITE_FC, TRAIN_SITE_FFN = 0, 1, 2
+TRAIN_SAVED = {"ffn_hidden": 0, "attn_prob": 1, "attn_out": 2, "attn_ln": 3, "layer_out": 4, "layer_in": 5}
+TRAIN_MAX_L = 197        # the longest window + 1 the training step accepts
+TRAIN_GRAD_CHUNK = 512   # rows per partial of a weight / bias gradient sum (csrc/train_step.h)
 EVAL_METRIC_KEYS = ("root_dist", "root_rot_dist", "root_trans_dist", "head_dist", "head_rot_dist", "head_trans_dist", "mpjpe",
                     "mpjpe_wo_hand", "accel_pred", "accel_gt", "accel_err", "pred_fs", "gt_fs")  # then single_jpe[22]
 EVAL_N_METRICS = len(EVAL_METRIC_KEYS) + 22
@@ -203,6 +210,22 @@ def load():
     lib.egoego_amass_floor_workspace_bytes.restype = sz
     lib.egoego_amass_floor_contacts.argtypes = [vp, C.POINTER(C.c_int32), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.egoego_amass_head.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.egoego_train_last_error.restype = C.c_char_p
+    lib.egoego_train_ctx_create.argtypes = [C.POINTER(Config), i32, C.POINTER(vp)]
+    lib.egoego_train_ctx_destroy.argtypes = [vp]
+    lib.egoego_train_ctx_destroy.restype = None
+    lib.egoego_train_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.egoego_train_workspace_bytes.restype = sz
+    lib.egoego_train_saves_bytes.argtypes = [vp, i32, i32]
+    lib.egoego_train_saves_bytes.restype = sz
+    # ctx, weights, x_start, noise, cond_noise, cond_mask, t, row_mask, 3 schedule tables, objective, loss type, p_drop, seed, window ids,
+    # B, T, saves, bytes, workspace, bytes, loss, model_out, stream
+    lib.egoego_train_forward.argtypes = [vp, C.POINTER(Weights), vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, u64, vp, i32, i32,
+                                         vp, sz, vp, sz, vp, vp, vp]
+    # ctx, weights, saves, bytes, upstream, grads (the layout of Weights), p_drop, seed, B, T, workspace, bytes, stream
+    lib.egoego_train_backward.argtypes = [vp, C.POINTER(Weights), vp, sz, vp, C.POINTER(Weights), C.c_float, u64, i32, i32, vp, sz, vp]
+    lib.egoego_train_dropout_mask.argtypes = [vp, C.c_float, u64, i32, i32, vp, i32, i32, vp, vp, sz, vp]
+    lib.egoego_train_saved.argtypes = [vp, vp, sz, i32, i32, i32, i32, vp, vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -230,3 +253,4 @@ check_body = _checker("body-model ", "egoego_body_last_error")
 check_eval = _checker("evaluation ", "egoego_eval_last_error")
 check_win = _checker("motion-window ", "egoego_win_last_error")
 check_amass = _checker("AMASS-preprocessing ", "egoego_amass_last_error")
+check_train = _checker("training-step ", "egoego_train_last_error")

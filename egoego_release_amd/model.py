@@ -10,8 +10,11 @@ load key-for-key (state_dict layout in SURVEY.md §8b).
 
 The nn.Modules below hold parameters only.  Every SAMPLING method runs on the HIP library and raises
 if it is unavailable or the tensors are not on a ROCm device — there is no PyTorch/CPU fallback.
-The plain-PyTorch `forward` of the parameter containers exists solely for the training loss
-(`p_losses` / `forward`), which is outside the accelerated path.
+The training loss (`p_losses` / `forward`) has two paths.  By default it is the plain-PyTorch `forward` of
+the parameter containers under autograd, exactly as before.  With `hip_training = True` the loss and the
+gradient of every trainable tensor come from the HIP training step (train.py, csrc/train_step.*) behind the
+same signature, so `loss.backward(); optimizer.step()` runs unchanged; like sampling, that path raises on
+a CPU tensor instead of falling back.
 """
 import math
 import warnings
@@ -162,6 +165,7 @@ class _EngineSlot:
         self.force_repack = False  # ... and asked for the re-pack that applies it (a re-pack for any other reason clears `demoted`)
         self.unprobed_work = 0     # steps sampled on a "small job" context (split-bf16, no probe): plan.is_small_job
         self.caller_checked = False  # the plan was measured once more on a caller's conditions (at most once per packed weights)
+        self.train_engine = None     # the context of the HIP training step (hip_training): holds no weights, so nothing invalidates it
 
     def __deepcopy__(self, memo):
         return _EngineSlot()
@@ -232,6 +236,7 @@ class CondGaussianDiffusion(nn.Module):
         self.hip_outlier_guard = True     # False: no read-back (and no stream sync) at the end of a chain
         self.hip_outlier_seen = None      # per LayerNorm site, the largest row maximum of the last guarded chain
         self.hip_graph = True        # replay one captured step per chain (hipGraph); False launches every kernel
+        self.hip_training = False    # True: p_losses / forward compute the loss and its gradients on the HIP training step (train.py)
         self.sampling_rng = "torch"  # "torch": reference RNG draw order; "philox": in-kernel, shard-invariant
         self.philox_seed = 0
         self._slot = _EngineSlot()
@@ -654,7 +659,7 @@ class CondGaussianDiffusion(nn.Module):
                                                          noise=noise, parents=parents, window_offset=window_offset,
                                                          sampler=sampler, n_steps=n_steps, eta=eta)
 
-    # ------------------------------------------------------------------ training half (plain PyTorch)
+    # ------------------------------------------------------------------ training half (plain PyTorch, or HIP with hip_training)
     def q_sample(self, x_start, t, noise=None):
         noise = torch.randn_like(x_start) if noise is None else noise
         return (_extract(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
@@ -668,7 +673,40 @@ class CondGaussianDiffusion(nn.Module):
             return F.mse_loss
         raise ValueError(f"invalid loss type {self.loss_type}")
 
+    def _train_engine(self):
+        """The HIP training-step context for the module's device (built lazily; it holds no copy of the weights)."""
+        from . import train
+        dev = self.betas.device
+        if dev.type != "cuda":
+            raise _lib.EgoEgoHipError(
+                "hip_training is set: the training loss runs on the MI355X HIP path only: move the module and its inputs to a "
+                f"ROCm device first (the module is on {dev}); there is no CPU fallback")
+        eng = self._slot.train_engine
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        if eng is None or eng.dev_index != idx:
+            if eng is not None:
+                eng.close()
+            eng = self._slot.train_engine = train.TrainEngine(_engine_cfg(self), dev)
+        return eng
+
+    def _p_losses_hip(self, x_start, cond_mask, t, noise=None, padding_mask=None):
+        """p_losses on the HIP training step: the same torch draws in the same order (noise, then the condition noise), plus one
+        host-side torch.randint for the dropout seed, so torch.manual_seed fixes a run."""
+        from . import train
+        if x_start.device.type != "cuda":
+            raise _lib.EgoEgoHipError(f"hip_training is set: x_start is on {x_start.device}; the HIP training step has no CPU fallback")
+        eng = self._train_engine()
+        if self.objective not in ("pred_noise", "pred_x0"):
+            raise ValueError(f"unknown objective {self.objective}")
+        self.loss_fn  # (raises on an invalid loss type, like the plain path)
+        noise = torch.randn_like(x_start) if noise is None else noise
+        cond_noise = torch.randn_like(x_start)
+        seed = int(torch.randint(0, 2 ** 62, (1,)))
+        return train.training_loss(self, eng, x_start, cond_mask, t, noise, cond_noise, padding_mask, seed)
+
     def p_losses(self, x_start, cond_mask, t, noise=None, padding_mask=None):
+        if self.hip_training:
+            return self._p_losses_hip(x_start, cond_mask, t, noise=noise, padding_mask=padding_mask)
         noise = torch.randn_like(x_start) if noise is None else noise
         x = self.q_sample(x_start=x_start, t=t, noise=noise)
         x_cond = x_start * (1.0 - cond_mask) + cond_mask * torch.randn_like(x_start)

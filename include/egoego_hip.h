@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*), the motion windows (egoego_win_*), the ragged sampling entry points (egoego_*_ragged) and the AMASS preprocessing (egoego_amass_*) were added under 8: purely additive, no existing entry changed */
+#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*), the motion windows (egoego_win_*), the ragged sampling entry points (egoego_*_ragged) the AMASS preprocessing (egoego_amass_*) and the stage-2 training step (egoego_train_*) were added under 8: purely additive, no existing entry changed */
 
 enum {
     EGOEGO_OK = 0,
@@ -596,6 +596,81 @@ int egoego_amass_head(const float* d_joints, const float* d_head_rot, const floa
                       const int32_t* d_src, const int32_t* d_seq, const int32_t* d_out_offsets, int n_out, int n_frames, int B,
                       float* d_joints_out, double* d_contacts_out, float* d_head_trans, float* d_rot6d, float* d_qpos, float* d_rot6d_diff,
                       float* d_trans_diff, float* d_vels, uint8_t* d_same, void* stream);
+
+/* ==================================================================================================================
+ * The stage-2 training step (egoego_train_*; added under ABI 8, purely additive): the loss of CondGaussianDiffusion.p_losses
+ * (M:574-605) and the gradient of every trainable tensor of the denoiser, on split-bf16 MFMAs (three bf16 MFMAs per product, fp32
+ * accumulate; LayerNorm, softmax, GELU, residuals and the loss in fp32, the loss summed in fp64 in a fixed order).  Shapes:
+ * d_model 512, 4 heads, d_k = d_v = 256, FFN 512; n_dec_layers and d_feats from the config; T + 1 <= 197.
+ *   - the weights are the caller's LIVE fp32 parameter tensors (egoego_weights, device pointers): every call reads them in place
+ *     and splits them as it loads them, so a call after an optimizer step sees the new values; nothing is packed or cached.
+ *   - a call only enqueues work on `stream`: no allocation, no host copy, no synchronisation.
+ *   - `saves` is a caller-allocated buffer (256-byte aligned, egoego_train_saves_bytes) that egoego_train_forward fills and
+ *     egoego_train_backward reads: one per outstanding graph.  The workspace (egoego_train_workspace_bytes) is scratch of one call;
+ *     what either buffer holds on entry to egoego_train_forward is irrelevant, as for every other workspace of this library.
+ *   - every sum over the B * (T + 1) rows (weight, bias and LayerNorm gradients) runs over fixed chunks of rows whose partials are
+ *     added in chunk order, without float atomics: loss and gradients have the same bits on every run.
+ *   - dropout (TM:63, 68, 108: attention probabilities, fc output, FFN output) draws in-kernel Philox4x32-10 keyed by
+ *     (seed; layer, site, window id, element index within the window); the backward pass regenerates the masks.  p_drop = 0: none.
+ * egoego_train_last_error() describes the last failure of an egoego_train_* call.
+ * ================================================================================================================== */
+typedef struct egoego_train_ctx egoego_train_ctx;
+enum { EGOEGO_LOSS_L1 = 0, EGOEGO_LOSS_L2 = 1 };  /* M:563-571 */
+enum { EGOEGO_TRAIN_SITE_ATTN = 0, EGOEGO_TRAIN_SITE_FC = 1, EGOEGO_TRAIN_SITE_FFN = 2 };
+/* egoego_train_saved: [B][T+1][512] unless noted */
+enum { EGOEGO_TRAIN_SAVED_FFN_HIDDEN = 0,  /* relu(w_1 . + b_1) */
+       EGOEGO_TRAIN_SAVED_ATTN_PROB = 1,   /* [B][4][T+1][T+1], before dropout */
+       EGOEGO_TRAIN_SAVED_ATTN_OUT = 2,    /* [B][T+1][1024] */
+       EGOEGO_TRAIN_SAVED_ATTN_LN = 3,     /* the attention sublayer's output */
+       EGOEGO_TRAIN_SAVED_LAYER_OUT = 4,
+       EGOEGO_TRAIN_SAVED_LAYER_IN = 5 };
+
+/* Caller-allocated fp32 device buffers, one per trainable tensor, in the layout of egoego_weights (conv weights (out, in, 1)).
+ * position_vec is frozen: its slot is not read. */
+typedef struct {
+    float* w_q; float* b_q; float* w_k; float* b_k; float* w_v; float* b_v; float* w_fc; float* b_fc; float* ln1_g; float* ln1_b;
+    float* w_1; float* b_1; float* w_2; float* b_2; float* ln2_g; float* ln2_b;
+} egoego_train_layer_grads;
+typedef struct {
+    float* start_conv_w; float* start_conv_b;
+    float* position_vec;  /* unused */
+    float* linear_out_w; float* linear_out_b;
+    float* time_mlp1_w; float* time_mlp1_b;
+    float* time_mlp3_w; float* time_mlp3_b;
+    const egoego_train_layer_grads* layers;  /* HOST array of n_dec_layers entries */
+} egoego_train_grads;
+
+const char* egoego_train_last_error(void);
+/* cfg: the shapes of egoego_config (objective, precision and flags are not read). */
+int egoego_train_ctx_create(const egoego_config* cfg, int device, egoego_train_ctx** out);
+void egoego_train_ctx_destroy(egoego_train_ctx* ctx);
+/* 0 (egoego_train_last_error() says why) for a shape no call accepts. */
+size_t egoego_train_workspace_bytes(const egoego_train_ctx* ctx, int B, int T);
+size_t egoego_train_saves_bytes(const egoego_train_ctx* ctx, int B, int T);
+/* p_losses (M:574-605) with the caller's draws: d_x_start, d_noise, d_cond_noise, d_cond_mask [B][T][d_feats]; d_t int64 [B]
+ * (clamped to the schedule); d_row_mask fp32 [B][T+1] (padding_mask[:, 0, :]) or NULL; the three schedule tables are DEVICE arrays
+ * of num_timesteps entries (sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, p2_loss_weight).  d_window_ids int64 [B] or NULL
+ * (window b has id b): the dropout streams.  Writes *d_loss (device scalar) and, when not NULL, d_model_out [B][T][d_feats].
+ * The rows of d_model_out of a window depend on that window's own inputs and id only. */
+int egoego_train_forward(egoego_train_ctx* ctx, const egoego_weights* w, const float* d_x_start, const float* d_noise,
+                         const float* d_cond_noise, const float* d_cond_mask, const int64_t* d_t, const float* d_row_mask,
+                         const float* d_sqrt_alphas_cumprod, const float* d_sqrt_one_minus_alphas_cumprod, const float* d_p2_loss_weight,
+                         int objective, int loss_type, float p_drop, uint64_t dropout_seed, const int64_t* d_window_ids, int B, int T,
+                         void* d_saves, size_t saves_bytes, void* d_workspace, size_t workspace_bytes, float* d_loss, float* d_model_out,
+                         void* stream);
+/* The gradient of d_upstream[0] * loss for every buffer of `grads` (overwritten), from the saves of the forward call with the same
+ * weights, p_drop, dropout_seed, B and T.  d_upstream is a DEVICE scalar: the product is taken on the device, and a power of two
+ * scales every gradient exactly. */
+int egoego_train_backward(egoego_train_ctx* ctx, const egoego_weights* w, const void* d_saves, size_t saves_bytes,
+                          const float* d_upstream, const egoego_train_grads* grads, float p_drop, uint64_t dropout_seed, int B, int T,
+                          void* d_workspace, size_t workspace_bytes, void* stream);
+/* The mask (1 keep / 0 drop, one byte each) a forward call with these arguments applies at `site` of `layer`: site 0
+ * [B][4][T+1][T+1], sites 1 and 2 [B][T+1][512].  The workspace holds the implied window ids when d_window_ids is NULL (8 B bytes). */
+int egoego_train_dropout_mask(egoego_train_ctx* ctx, float p_drop, uint64_t dropout_seed, int layer, int site, const int64_t* d_window_ids,
+                              int B, int T, uint8_t* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Test/debug: copies saved tensor `which` (EGOEGO_TRAIN_SAVED_*) of `layer` out of the saves of a forward call. */
+int egoego_train_saved(egoego_train_ctx* ctx, const void* d_saves, size_t saves_bytes, int B, int T, int layer, int which, float* d_out,
+                       void* stream);
 
 #ifdef __cplusplus
 }

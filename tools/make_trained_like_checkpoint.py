@@ -23,8 +23,10 @@ from egoego_release_amd import ModelConfig, make_weights, head_condition_mask  #
 from egoego_release_amd.synthetic import make_motion_windows  # noqa: E402
 
 
-def train_like(steps=3000, seed=0, device=None, T=120, batch=32, lr=2e-4, log_every=0, pool=4096):
-    """Returns (state_dict on the CPU, info).  Deterministic given (steps, seed, T, batch, lr) on one device type.
+def train_like(steps=3000, seed=0, device=None, T=120, batch=32, lr=2e-4, log_every=0, pool=4096, hip=False):
+    """Returns (state_dict on the CPU, info).  Deterministic given (steps, seed, T, batch, lr, hip) on one device type.
+    hip=True: loss and gradients come from the HIP training step (model.hip_training; needs a ROCm device) instead of autograd
+    over the plain-PyTorch forward; the draws of t and of the noises are the same, the dropout masks are not.
     lr: twice the reference's 1e-4 (trainer:39); 1e-3 collapses the post-LN stack to the mean pose within 2000 steps (measured, round 4)."""
     from egoego_release_amd.model import CondGaussianDiffusion
 
@@ -33,6 +35,7 @@ def train_like(steps=3000, seed=0, device=None, T=120, batch=32, lr=2e-4, log_ev
     model = CondGaussianDiffusion(**cfg.ctor_kwargs())
     model.load_state_dict(make_weights(cfg, seed), strict=False)
     model = model.to(dev)
+    model.hip_training = bool(hip)
     model.train()
     data = make_motion_windows(pool, T, seed=seed + 1, device=dev)
     mask = head_condition_mask((batch, T, cfg.d_feats), device=dev)
@@ -55,7 +58,7 @@ def train_like(steps=3000, seed=0, device=None, T=120, batch=32, lr=2e-4, log_ev
     model.invalidate_engine()
     sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     gains = [v.abs() for k, v in sd.items() if k.endswith("layer_norm.weight")]
-    info = {"steps": steps, "seed": seed, "lr": lr, "batch": batch, "T": T, "device": str(dev), "seconds": time.time() - t0,
+    info = {"steps": steps, "seed": seed, "lr": lr, "batch": batch, "T": T, "device": str(dev), "hip": bool(hip), "seconds": time.time() - t0,
             "loss_first": first, "loss_last": last,
             "gain_spread": max(float(a.max() / a.median()) for a in gains),
             "beta_absmax": max(float(v.abs().max()) for k, v in sd.items() if k.endswith("layer_norm.bias"))}
@@ -71,8 +74,9 @@ def main():
     ap.add_argument("--window", type=int, default=120)
     ap.add_argument("--device", default=None)
     ap.add_argument("--out", default="trained_like.pt")
+    ap.add_argument("--hip", action="store_true", help="train through the HIP training step (CondGaussianDiffusion.hip_training)")
     args = ap.parse_args()
-    sd, info = train_like(args.steps, args.seed, args.device, args.window, args.batch, args.lr, log_every=max(1, args.steps // 10))
+    sd, info = train_like(args.steps, args.seed, args.device, args.window, args.batch, args.lr, log_every=max(1, args.steps // 10), hip=args.hip)
     # the reference's checkpoint layout (Trainer.save, trainer_amass_cond_motion_diffusion.py:99-106; ema-pytorch prefixes)
     torch.save({"step": args.steps, "model": sd, "ema": {"ema_model." + k: v for k, v in sd.items()}, "scaler": {}}, args.out)
     print(info)
