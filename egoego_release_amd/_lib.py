@@ -81,7 +81,7 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_profile_begin", "egoego_profile_end", "egoego_debug_stage", "egoego_last_kernel_name", "egoego_outlier_stats",
            "egoego_s1_last_error", "egoego_s1_ctx_create", "egoego_s1_ctx_destroy", "egoego_s1_load_weights",
            "egoego_s1_workspace_bytes", "egoego_s1_encode", "egoego_s1_gravity_features", "egoego_s1_integrate",
-           "egoego_s1_gravity_apply", "egoego_flow_last_error", "egoego_flow_ctx_create", "egoego_flow_ctx_destroy",
+           "egoego_s1_gravity_apply", "egoego_s1_gravity_align", "egoego_s1_head_pose_metrics", "egoego_flow_last_error", "egoego_flow_ctx_create", "egoego_flow_ctx_destroy",
            "egoego_flow_load_weights", "egoego_flow_workspace_bytes", "egoego_flow_features",
            "egoego_body_last_error", "egoego_body_ctx_create", "egoego_body_ctx_destroy", "egoego_body_load_model",
            "egoego_body_workspace_bytes", "egoego_body_forward",
@@ -172,6 +172,8 @@ def load():
     lib.egoego_s1_gravity_features.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.egoego_s1_integrate.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp]
     lib.egoego_s1_gravity_apply.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.egoego_s1_gravity_align.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.egoego_s1_head_pose_metrics.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.egoego_flow_last_error.restype = C.c_char_p
     lib.egoego_flow_ctx_create.argtypes = [i32, i32, C.POINTER(vp)]
     lib.egoego_flow_ctx_destroy.argtypes = [vp]

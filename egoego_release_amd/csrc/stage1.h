@@ -474,4 +474,180 @@ __global__ void s1_gravity_apply_kernel(const float* rot, const float* trans, co
     }
 }
 
+// ------------------------------------------------------------------------------------------------ Rodrigues + planar Umeyama
+static constexpr int ALIGN_CHUNK = 512;  // frames of the trajectory held in LDS at a time
+
+EG_D double round_f32(double x) { return (double)(float)x; }
+
+// One wave per sequence.  Rn: head_normal_estimation_transformer.py:47-63 in fp64, rounded through fp32.  Ralign: the r of evo's
+// umeyama_alignment on est_i = p_0 + a_i (a as in s1_gravity_apply_kernel) and ref_i, both with z = 1, over n = min(len, ref_len)
+// frames.  With z constant the 3 x 3 covariance is the 2 x 2 matrix A = (1/n) sum (ref_i - mean_ref)(est_i - mean_est)^T bordered
+// by zeros, and u s v with evo's determinant fix is blockdiag(Q, det Q), Q the orthogonal polar factor of A:
+//   det A >= 0:  Q = [[e, -f], [f, e]] / hypot(e, f),  e = A00 + A11, f = A10 - A01   (rotation)
+//   det A <  0:  Q = [[e, f], [f, -e]] / hypot(e, f),  e = A00 - A11, f = A01 + A10   (reflection)
+// Order: per chunk of ALIGN_CHUNK frames the lanes compute Rn (p_i - p_{i-1}) into LDS, lane 0 runs the serial chain over it, and
+// lane l sums frames l, l + 64, ... in fp64; pass 0 gives the means, pass 1 the covariance; the 64 partials are folded in lane
+// order.  Nothing depends on S, Lmax or Rmax.
+__global__ __launch_bounds__(64) void s1_gravity_align_kernel(const float* trans, const int* len, int Lmax, const float* normal,
+                                                              const double* scl, const double* ref, const int* ref_len, int Rmax,
+                                                              double* Rn_out, double* Ral_out) {
+    __shared__ double axy[ALIGN_CHUNK][2];
+    __shared__ double part[64][4];
+    __shared__ double carry[2];
+    __shared__ double tot[4];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    double rn[9];
+    {
+        const double n0 = normal[3 * s], n1 = normal[3 * s + 1], n2 = normal[3 * s + 2];
+        const double nn = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+        const double a0 = n0 / nn, a1 = n1 / nn, a2 = n2 / nn;
+        const double v0 = a1, v1 = -a0, v2 = 0.0;  // a x (0, 0, 1)
+        const double c = a2, sn = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+        const double k[9] = {0.0, -v2, v1, v2, 0.0, -v0, -v1, v0, 0.0};
+        double kk[9];
+        mat3mul(k, k, kk);
+        const double g = (1.0 - c) / (sn * sn);
+        for (int j = 0; j < 9; ++j) rn[j] = round_f32((j % 4 == 0 ? 1.0 : 0.0) + k[j] + kk[j] * g);
+    }
+    if (lane < 9) Rn_out[9 * s + lane] = rn[lane];
+    const int n = max(0, min(min(len[s], Lmax), min(ref_len[s], Rmax)));
+    const double sc = scl[s];
+    const float* P = trans + (size_t)s * Lmax * 3;
+    const double* Rf = ref + (size_t)s * Rmax * 7;
+    const double p0x = n > 0 ? (double)P[0] : 0.0, p0y = n > 0 ? (double)P[1] : 0.0;
+    double mean[4] = {0, 0, 0, 0};  // est x, est y, ref x, ref y
+    double A[4] = {0, 0, 0, 0};
+    for (int pass = 0; pass < 2; ++pass) {
+        double acc[4] = {0, 0, 0, 0};
+        if (lane == 0) carry[0] = carry[1] = 0.0;
+        for (int c0 = 0; c0 < n; c0 += ALIGN_CHUNK) {
+            const int m = min(ALIGN_CHUNK, n - c0);
+            __syncthreads();
+            for (int j = lane; j < m; j += 64) {
+                const int i = c0 + j;
+                double dx = 0.0, dy = 0.0;
+                if (i > 0) {
+                    const double d[3] = {(double)P[3 * i] - P[3 * i - 3], (double)P[3 * i + 1] - P[3 * i - 2], (double)P[3 * i + 2] - P[3 * i - 1]};
+                    dx = rn[0] * d[0] + rn[1] * d[1] + rn[2] * d[2];
+                    dy = rn[3] * d[0] + rn[4] * d[1] + rn[5] * d[2];
+                }
+                axy[j][0] = dx;
+                axy[j][1] = dy;
+            }
+            __syncthreads();
+            if (lane == 0) {
+                double ax = carry[0], ay = carry[1];
+                for (int j = 0; j < m; ++j) {
+                    if (c0 + j > 0) {
+                        ax += sc * axy[j][0];
+                        ay += sc * axy[j][1];
+                    }
+                    axy[j][0] = ax;
+                    axy[j][1] = ay;
+                }
+                carry[0] = ax;
+                carry[1] = ay;
+            }
+            __syncthreads();
+            for (int j = lane; j < m; j += 64) {
+                const int i = c0 + j;
+                const double ex = axy[j][0] + p0x, ey = axy[j][1] + p0y;
+                const double rx = Rf[(size_t)i * 7], ry = Rf[(size_t)i * 7 + 1];
+                if (pass == 0) {
+                    acc[0] += ex; acc[1] += ey; acc[2] += rx; acc[3] += ry;
+                } else {
+                    const double qx = ex - mean[0], qy = ey - mean[1], wx = rx - mean[2], wy = ry - mean[3];
+                    acc[0] += wx * qx; acc[1] += wx * qy; acc[2] += wy * qx; acc[3] += wy * qy;
+                }
+            }
+        }
+        __syncthreads();
+        for (int j = 0; j < 4; ++j) part[lane][j] = acc[j];
+        __syncthreads();
+        if (lane == 0) {
+            for (int j = 0; j < 4; ++j) {
+                double t = 0.0;
+                for (int l = 0; l < 64; ++l) t += part[l][j];
+                tot[j] = n > 0 ? t / n : 0.0;
+            }
+        }
+        __syncthreads();
+        for (int j = 0; j < 4; ++j) (pass == 0 ? mean : A)[j] = tot[j];
+    }
+    if (lane == 0) {
+        const bool rot = A[0] * A[3] - A[1] * A[2] >= 0.0;
+        const double e = rot ? A[0] + A[3] : A[0] - A[3];
+        const double f = rot ? A[2] - A[1] : A[1] + A[2];
+        const double h = hypot(e, f);
+        double q[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        if (h != 0.0) {  // (h == 0: a zero covariance, n <= 1 — the SVD path's answer for a zero matrix; NaN input stays NaN)
+            const double ce = round_f32(e / h), sf = round_f32(f / h);
+            q[0] = ce;
+            q[1] = rot ? -sf : sf;
+            q[3] = sf;
+            q[4] = rot ? ce : -ce;
+            q[8] = rot ? 1.0 : -1.0;
+        }
+        for (int j = 0; j < 9; ++j) Ral_out[9 * s + j] = q[j];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ stage-1 head-pose metrics
+// pytorch3d's quaternion_to_matrix (w, x, y, z; any norm), row-major
+EG_D void quat2mat_p3d(const double* q, double m[9]) {
+    const double r = q[0], i = q[1], j = q[2], k = q[3];
+    const double two_s = 2.0 / (r * r + i * i + j * j + k * k);
+    m[0] = 1 - two_s * (j * j + k * k); m[1] = two_s * (i * j - k * r);     m[2] = two_s * (i * k + j * r);
+    m[3] = two_s * (i * j + k * r);     m[4] = 1 - two_s * (i * i + k * k); m[5] = two_s * (j * k - i * r);
+    m[6] = two_s * (i * k - j * r);     m[7] = two_s * (j * k + i * r);     m[8] = 1 - two_s * (i * i + j * j);
+}
+
+// egoego/eval/head_pose_metrics.py:26-44, one wave per sequence: lane l sums frames l, l + 64, ... in fp64, the 64 partials are
+// folded in lane order and divided by the length.  out[b] = (head_dist, head_dist_rot_only, head_trans_err * 1000).
+__global__ __launch_bounds__(64) void s1_head_pose_metrics_kernel(const double* pred, const double* gt, const int* lengths, int Tmax,
+                                                                  double* out) {
+    __shared__ double part[64][3];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = max(0, min(lengths[b], Tmax));
+    double acc[3] = {0, 0, 0};
+    for (int t = lane; t < n; t += 64) {
+        const double* p = pred + ((size_t)b * Tmax + t) * 7;
+        const double* g = gt + ((size_t)b * Tmax + t) * 7;
+        double Rp[9], Rg[9], inv[9], E[9];
+        quat2mat_p3d(p + 3, Rp);
+        quat2mat_p3d(g + 3, Rg);
+        // Rg^-1 = adj(Rg) / det(Rg)
+        inv[0] = Rg[4] * Rg[8] - Rg[5] * Rg[7]; inv[1] = Rg[2] * Rg[7] - Rg[1] * Rg[8]; inv[2] = Rg[1] * Rg[5] - Rg[2] * Rg[4];
+        inv[3] = Rg[5] * Rg[6] - Rg[3] * Rg[8]; inv[4] = Rg[0] * Rg[8] - Rg[2] * Rg[6]; inv[5] = Rg[2] * Rg[3] - Rg[0] * Rg[5];
+        inv[6] = Rg[3] * Rg[7] - Rg[4] * Rg[6]; inv[7] = Rg[1] * Rg[6] - Rg[0] * Rg[7]; inv[8] = Rg[0] * Rg[4] - Rg[1] * Rg[3];
+        const double det = Rg[0] * inv[0] + Rg[1] * inv[3] + Rg[2] * inv[6];
+        for (int j = 0; j < 9; ++j) inv[j] /= det;
+        mat3mul(Rp, inv, E);
+        double fr = 0.0;
+        for (int j = 0; j < 9; ++j) {
+            const double d = (j % 4 == 0 ? 1.0 : 0.0) - E[j];
+            fr += d * d;
+        }
+        double Et[3];
+        mat3vec(E, g, Et);
+        double ft = 0.0, tt = 0.0;
+        for (int j = 0; j < 3; ++j) {
+            const double d = p[j] - Et[j], u = p[j] - g[j];
+            ft += d * d;
+            tt += u * u;
+        }
+        acc[0] += sqrt(fr + ft);
+        acc[1] += sqrt(fr);
+        acc[2] += sqrt(tt);
+    }
+    for (int j = 0; j < 3; ++j) part[lane][j] = acc[j];
+    __syncthreads();
+    if (lane < 3) {
+        double t = 0.0;
+        for (int l = 0; l < 64; ++l) t += part[l][lane];
+        t /= n;  // a length of 0 gives NaN: the mean of no frames
+        out[3 * b + lane] = lane == 2 ? t * 1000.0 : t;
+    }
+}
+
 }  // namespace s1

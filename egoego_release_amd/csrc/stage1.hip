@@ -270,4 +270,26 @@ int egoego_s1_gravity_apply(const float* d_rot, const float* d_trans, const int3
     return 0;
 }
 
+int egoego_s1_gravity_align(const float* d_rot, const float* d_trans, const int32_t* d_len, int Sn, int Lmax, const float* d_normal,
+                            const double* d_scale, const double* d_ref, const int32_t* d_ref_len, int Rmax, double* d_Rn,
+                            double* d_Ralign, void* stream) {
+    (void)d_rot;  // the alignment reads positions only
+    if (!d_trans || !d_len || !d_normal || !d_scale || !d_ref || !d_ref_len || !d_Rn || !d_Ralign || Sn < 1 || Lmax < 1 || Rmax < 1)
+        return fail(EGOEGO_E_INVALID, "bad argument");
+    s1_gravity_align_kernel<<<Sn, 64, 0, as_stream(stream)>>>(d_trans, (const int*)d_len, Lmax, d_normal, d_scale, d_ref,
+                                                              (const int*)d_ref_len, Rmax, d_Rn, d_Ralign);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EGOEGO_E_HIP, "launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int egoego_s1_head_pose_metrics(const double* d_pred, const double* d_gt, const int32_t* d_lengths, int Bn, int Tmax, double* d_out,
+                                void* stream) {
+    if (!d_pred || !d_gt || !d_lengths || !d_out || Bn < 1 || Tmax < 1) return fail(EGOEGO_E_INVALID, "bad argument");
+    s1_head_pose_metrics_kernel<<<Bn, 64, 0, as_stream(stream)>>>(d_pred, d_gt, (const int*)d_lengths, Tmax, d_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EGOEGO_E_HIP, "launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
 }  // extern "C"

@@ -253,3 +253,49 @@ def evaluate_samples(ds, local_aa, root_trans, gt_global_quat, gt_global_jpos, g
                                              best.data_ptr(), _stream(dev)))
     return {"metrics": _metrics_dict(table), "floor_height": floor, "contacts": contacts, "discard": discard, "global_quat": quat,
             "global_jpos": jpos, "root_trans": root, "best": best}
+
+
+def evaluate_pipeline(headnet, gravitynet, model, ds, batch, gt_root_trans, gt_local_aa, lengths, samples_per_sequence=1, fps=30,
+                      sequence_offset=0, **sampler_kw):
+    """eval_egoego.py:241-483 for a whole evaluation set of S sequences of different lengths in one call: ragged stage 1, its
+    score, the move onto the floor, ragged stage 2 and the full-body metrics.
+
+    batch: the stage-1 inputs, padded (of [S, Tmax, 512]; head_pose, aligned_slam_trans, ori_slam_trans, ori_slam_rot_mat
+    [S, Tmax + 1, ...]); lengths [S] (host integers or a CPU tensor): the feature frames T_s of each sequence — every pose-like
+    entry and the ground truth gt_root_trans [S, Tmax + 1, 3] / gt_local_aa [S, Tmax + 1, 22, 3] (SMPL root translation and local
+    axis-angle; the reference's qpos conversion is the caller's) hold T_s + 1 frames.  sampler_kw goes to
+    full_body_gen_cond_head_pose_sliding_window_ragged (sampler, n_steps, eta, noise, parents).
+
+      lines 275-294   GravityNet's translation with HeadNet's rotation, the xy of the first frame taken off
+      lines 296-312   the stage-1 metrics against batch['head_pose'] with the same xy shift
+      lines 327-335   FK of the ground truth, its floor height off z, the head trajectory moved onto its first head joint
+      lines 358-446   stage 2 and evaluate_samples(..., lengths=, group=): sample j of sequence s is row s * n + j, group s
+
+    -> evaluate_samples' dictionary plus stage1_metrics [S, 3] float64 (head_dist, head_dist_rot_only, head_trans_err in mm),
+    head_pose [S, Tmax + 1, 7] float64 (what stage 2 was conditioned on, zero past each end) and lengths [S] (CPU, T_s + 1).
+    A sequence's numbers are the same bits alone (with sequence_offset moved on by its index) and in any batch."""
+    from . import harness, stage1
+    hp, _, _, n = stage1.stage1_ragged(headnet, gravitynet, batch, lengths)
+    dev = _device_of(hp, "the stage-1 head pose")
+    S, N = hp.shape[:2]
+    n_dev = torch.as_tensor(n, dtype=torch.int64).to(dev)
+    hp[:, :, :2] -= hp[:, 0:1, :2].clone()
+    gt_pose = torch.as_tensor(batch["head_pose"]).to(dev).double()[:, :N].clone()
+    gt_pose[:, :, :2] -= gt_pose[:, 0:1, :2].clone()
+    s1 = stage1.head_pose_metrics(hp, gt_pose, n_dev)
+    root_gt, aa_gt = torch.as_tensor(gt_root_trans).to(dev)[:, :N], torch.as_tensor(gt_local_aa).to(dev)[:, :N]
+    parents = sampler_kw.get("parents")
+    gq, gp = fk_smpl(root_gt, aa_gt, ds.rest_human_offsets, _parents_of(ds, parents))
+    floor, _, _ = determine_floor_height_and_contacts(gp, fps, n)
+    gp[:, :, :, 2] -= floor[:, None, None]
+    hp[:, :, :3] += gp[:, 0:1, HEAD_IDX, :].double() - hp[:, 0:1, :3]
+    hp = stage1._keep_rows(hp, n_dev)
+    n_smp = int(samples_per_sequence)
+    aa, root, out_len = harness.full_body_gen_cond_head_pose_sliding_window_ragged(
+        model, ds, hp, samples_per_sequence=n_smp, sequence_offset=sequence_offset, lengths=n, **sampler_kw)
+    Tp = aa.shape[1]
+    rep = lambda t: t[:, :Tp].repeat_interleave(n_smp, 0) if n_smp > 1 else t[:, :Tp]  # noqa: E731
+    group = torch.arange(S, device=dev).repeat_interleave(n_smp)
+    res = evaluate_samples(ds, aa, root, rep(gq), rep(gp), 0., lengths=out_len, group=group, fps=fps, parents=parents)
+    res.update(stage1_metrics=s1, head_pose=hp, lengths=torch.as_tensor(n, dtype=torch.int64))
+    return res

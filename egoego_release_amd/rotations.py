@@ -37,8 +37,8 @@ def matrix_to_quaternion(m):
         torch.stack((m02 - m20, m10 + m01, q_abs[..., 2] ** 2, m12 + m21), -1),
         torch.stack((m10 - m01, m20 + m02, m21 + m12, q_abs[..., 3] ** 2), -1)), -2)
     cand = cand / (2.0 * q_abs[..., None].clamp(min=0.1))
-    best = F.one_hot(q_abs.argmax(-1), 4) > 0.5
-    return standardize_quaternion(cand[best, :].reshape(m.shape[:-2] + (4,)))
+    best = q_abs.argmax(-1)[..., None, None].expand(m.shape[:-2] + (1, 4))  # (a gather: a boolean mask would wait for the device)
+    return standardize_quaternion(cand.gather(-2, best).squeeze(-2))
 
 
 def quaternion_raw_multiply(a, b):

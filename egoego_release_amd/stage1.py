@@ -10,9 +10,11 @@ Reference files (paths relative to the reference root):
     RE = run_egoego.py                                        (the pipeline)
 
 Every per-token and per-frame step runs in libegoego_hip (egoego_s1_*): the decoder and the MLP heads (split-bf16 MFMAs), the
-GravityNet input features, the angular-velocity integration with the SLAM rescale, and GravityNet's trajectory.  The host keeps
-what the reference itself does in numpy on 3 x 3 matrices: the rotation from the predicted floor normal (Rodrigues, HN:47-63) and
-the Umeyama alignment (evo's PoseTrajectory3D.align).  torch is plumbing only; there is no fallback.
+GravityNet input features, the angular-velocity integration with the SLAM rescale, and GravityNet's trajectory.  In the
+equal-length calls the host keeps what the reference itself does in numpy on 3 x 3 matrices: the rotation from the predicted floor
+normal (Rodrigues, HN:47-63) and the Umeyama alignment (evo's PoseTrajectory3D.align); with `lengths=` (sequences of different
+lengths in one call) both run in egoego_s1_gravity_align and nothing returns to the host.  compute_head_pose_metrics is the
+stage-1 score (egoego/eval/head_pose_metrics.py) on the device.  torch is plumbing only; there is no fallback.
 
 FlowFeatureExtractor turns raw optical flow into those features (RN's ResNet-18, egoego_flow_* in libegoego_hip).
 """
@@ -44,6 +46,35 @@ def block_spans(T, window):
 def gravity_valid_frames(L, window):
     """HN:122-141: a SLAM trajectory of L frames is truncated to window + 1 frames; the number of valid feature rows is L' - 1."""
     return max(min(L, window + 1) - 1, 0)
+
+
+def _host_lengths(lengths, B, hi, what, lo=1):
+    """`lengths` (host integers or a CPU tensor) -> list of B ints in lo..hi.  A device tensor is refused: the pack of a ragged
+    call is built on the host, and reading lengths back would wait for the device."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.device.type != "cpu":
+            raise ValueError(f"{what} must be host integers or a CPU tensor (the ragged pack is built on the host)")
+        lengths = lengths.reshape(-1).tolist()
+    a = [int(v) for v in np.asarray(lengths).reshape(-1).tolist()]
+    if len(a) != B:
+        raise ValueError(f"{what}: {len(a)} values for {B} sequences")
+    if a and (min(a) < lo or max(a) > hi):
+        raise ValueError(f"{what} span {min(a)}..{max(a)}: {lo}..{hi} (the padded length) expected")
+    return a
+
+
+def _upload(values, dtype, device):
+    """Host values -> a device tensor through pinned memory, without waiting for the device."""
+    t = torch.as_tensor(np.asarray(values), dtype=dtype)
+    if device.type != "cuda":
+        return t.to(device)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def _keep_rows(x, n):
+    """x [B, T, ...] with rows t >= n[b] (n a device tensor [B]) set to zero, whatever they held (NaN included)."""
+    m = torch.arange(x.shape[1], device=x.device)[None, :] < n[:, None]
+    return torch.where(m.reshape(m.shape + (1,) * (x.dim() - 2)), x, torch.zeros((), dtype=x.dtype, device=x.device))
 
 
 def _check_cfg(cfg, input_of_feats=True):
@@ -216,8 +247,9 @@ class HeadFormer(_Stage1Module):
         super().__init__(cfg, device, bool(_opt_get(opt, "input_of_feats", False)))
         self.transformer_window_size = opt.window
 
-    def _integrate(self, heads, T, q0, slam, W0, dist_scale):
-        """heads [W, window, 4] cuda; T / W0 per sequence; q0 [B, 4]; slam [B, L, 3] -> quats [B, max T + 1, 4], trans, scale (fp64)."""
+    def _integrate(self, heads, T, q0, slam, W0, dist_scale, lens=None):
+        """heads [W, window, 4] cuda; T / W0 per sequence; q0 [B, 4]; slam [B, L, 3] (lens: its valid frames per sequence, None =
+        all L) -> quats [B, max T + 1, 4], trans, scale (fp64); rows past a sequence's end stay zero."""
         dev = heads.device
         B = q0.shape[0]
         L = slam.shape[1]
@@ -227,7 +259,7 @@ class HeadFormer(_Stage1Module):
         scale = torch.zeros(B, dtype=torch.float64, device=dev)
         Tt = torch.tensor(T, dtype=torch.int32, device=dev)
         w0 = torch.tensor(W0, dtype=torch.int32, device=dev)
-        ln = torch.full((B,), L, dtype=torch.int32, device=dev)
+        ln = torch.full((B,), L, dtype=torch.int32, device=dev) if lens is None else torch.tensor(lens, dtype=torch.int32, device=dev)
         q0d = q0.to(dev, torch.float64).contiguous()
         sl = slam.to(dev, torch.float64).contiguous()
         eng = self.engine()
@@ -257,9 +289,19 @@ class HeadFormer(_Stage1Module):
         out["head_dist_scalar"] = heads[:, :T, 3:4]
         return out
 
-    def forward_for_eval(self, data):
+    def forward_for_eval(self, data, lengths=None, pose_lengths=None):
         """HE:214-308 for B sequences of equal length T at once: every block of every sequence in one encode call.
-        Extra keys: head_va [B, T, 3], head_dist_scalar [B, T, 1] (before / dist_scale), head_rot_quat [B, T + 1, 4]."""
+        Extra keys: head_va [B, T, 3], head_dist_scalar [B, T, 1] (before / dist_scale), head_rot_quat [B, T + 1, 4].
+
+        With `lengths` (host integers or a CPU tensor [B]) the sequences differ in length: data['of'] is [B, Tmax, 512] with
+        lengths[b] feature frames, the pose-like entries (head_pose, aligned_slam_trans) are [B, Lmax, ...] with pose_lengths[b]
+        frames (default lengths + 1).  Sequence b contributes len(block_spans(T_b, window)) blocks to the one encode call.  Every
+        output is zero past its sequence's end; pred_scale is always [B]; out['lengths'] (CPU) = min(L_b, T_b + 1), the valid
+        frames of head_pose.  What the padded frames of the inputs hold is never read."""
+        if lengths is not None:
+            return self._forward_for_eval_ragged(data, lengths, pose_lengths)
+        if pose_lengths is not None:
+            raise ValueError("pose_lengths needs lengths")
         eng = self.engine()
         x = torch.as_tensor(data["of"]).to(eng.device).float()
         B, T, F = x.shape
@@ -282,6 +324,47 @@ class HeadFormer(_Stage1Module):
         out["head_va"] = hv[..., :3]
         out["head_dist_scalar"] = hv[..., 3:4]
         out["head_rot_quat"] = quat
+        return out
+
+    def _forward_for_eval_ragged(self, data, lengths, pose_lengths):
+        x = torch.as_tensor(data["of"])
+        slam = torch.as_tensor(data["aligned_slam_trans"])
+        hp = torch.as_tensor(data["head_pose"])
+        if x.dim() != 3 or slam.dim() != 3 or hp.dim() != 3 or not x.shape[0] == slam.shape[0] == hp.shape[0]:
+            raise ValueError(f"of {tuple(x.shape)}, aligned_slam_trans {tuple(slam.shape)}, head_pose {tuple(hp.shape)}: "
+                             "[B, Tmax, F], [B, Lmax, 3], [B, >= 1, 7] expected")
+        B, Tmax, F = x.shape
+        T = _host_lengths(lengths, B, Tmax, "lengths")
+        L = _host_lengths(pose_lengths if pose_lengths is not None else [t + 1 for t in T], B, slam.shape[1], "pose_lengths")
+        eng = self.engine()
+        dev, win = eng.device, self.cfg.window
+        # the pack, from the host-side lengths: block w of the call is rows src[w] of the flattened features (a row past the
+        # block's valid count repeats the sequence's first row: encode reads it as zero), token (b, t) is row back[b, t] of heads
+        src, valid, win0 = [], [], []
+        back = np.zeros((B, Tmax), np.int64)
+        for b, Tb in enumerate(T):
+            win0.append(len(valid))
+            back[b, :Tb] = win0[b] * win + np.arange(Tb)
+            for st, n in block_spans(Tb, win):
+                r = np.full(win, b * Tmax, np.int64)
+                r[:n] = b * Tmax + st + np.arange(n)
+                src.append(r)
+                valid.append(n)
+        src = _upload(np.stack(src).reshape(-1), torch.int64, dev)
+        feats = x.to(dev).float().reshape(B * Tmax, F).index_select(0, src).reshape(len(valid), win, F)
+        heads = eng.encode(feats, _upload(valid, torch.int32, dev))
+        quat, trans, scale = self._integrate(heads, T, hp[:, 0, 3:], slam, win0, self.opt.dist_scale, lens=L)
+        n = [min(l, t + 1) for l, t in zip(L, T)]
+        N = max(n)
+        out = defaultdict(list)
+        out["head_pose"] = _keep_rows(torch.cat((trans[:, :N], quat[:, :N]), -1), _upload(n, torch.int64, dev))
+        out["pred_scale"] = scale
+        hv = _keep_rows(heads.reshape(-1, 4).index_select(0, _upload(back.reshape(-1), torch.int64, dev)).reshape(B, Tmax, 4),
+                        _upload(T, torch.int64, dev))
+        out["head_va"] = hv[..., :3]
+        out["head_dist_scalar"] = hv[..., 3:4]
+        out["head_rot_quat"] = quat
+        out["lengths"] = torch.tensor(n, dtype=torch.int64)
         return out
 
 
@@ -527,9 +610,19 @@ class HeadNormalFormer(_Stage1Module):
                                                           eng._stream()))
         return pose
 
-    def forward_for_eval(self, data, pred_scale=None, use_gt_aligned_rot=False):
+    def forward_for_eval(self, data, pred_scale=None, use_gt_aligned_rot=False, lengths=None, ref_lengths=None):
         """HN:214-294 for B sequences.  Extra keys: pred_normal [B, 3], normal_rot [B, 3, 3] (normal -> +z), align_rot [B, 3, 3]
-        (the Umeyama r)."""
+        (the Umeyama r).
+
+        With `lengths` (host integers or a CPU tensor [B]: the SLAM frames of each sequence in the padded head_trans /
+        head_rot_mat) the sequences differ in length, ref_lengths (default: lengths) counts the frames of ori_head_pose, and the
+        whole call stays on the device: features, encode, egoego_s1_gravity_align (the Rodrigues rotation and the planar Umeyama
+        alignment over min(length, ref_length) frames) and one egoego_s1_gravity_apply.  normal_rot and align_rot are then device
+        tensors, every per-frame output is zero past its sequence's end, out['lengths'] repeats the lengths."""
+        if lengths is not None:
+            return self._forward_for_eval_ragged(data, pred_scale, use_gt_aligned_rot, lengths, ref_lengths)
+        if ref_lengths is not None:
+            raise ValueError("ref_lengths needs lengths")
         normal = self.forward(data)["pred_normal"]
         rot, trans, ln = self._frames(data)
         B, L = rot.shape[:2]
@@ -566,11 +659,92 @@ class HeadNormalFormer(_Stage1Module):
         out["align_rot"] = torch.from_numpy(Ral)
         return out
 
+    def _forward_for_eval_ragged(self, data, pred_scale, use_gt_aligned_rot, lengths, ref_lengths):
+        if use_gt_aligned_rot:
+            raise NotImplementedError("use_gt_aligned_rot with lengths=: egoego_s1_gravity_align derives the rotation from the "
+                                      "predicted normal; run the equal-length call per sequence for the debugging path")
+        rot_in, trans_in, gt = (torch.as_tensor(data[k]) for k in ("head_rot_mat", "head_trans", "ori_head_pose"))
+        if rot_in.dim() != 4 or trans_in.dim() != 3 or gt.dim() != 3 or not rot_in.shape[:2] == trans_in.shape[:2] or gt.shape[0] != rot_in.shape[0]:
+            raise ValueError(f"head_rot_mat {tuple(rot_in.shape)}, head_trans {tuple(trans_in.shape)}, ori_head_pose "
+                             f"{tuple(gt.shape)}: [B, Lmax, 3, 3], [B, Lmax, 3], [B, Rmax, 7] expected")
+        B, Lmax = rot_in.shape[:2]
+        Rmax = gt.shape[1]
+        L = _host_lengths(lengths, B, Lmax, "lengths")
+        R = _host_lengths(ref_lengths if ref_lengths is not None else L, B, Rmax, "ref_lengths")
+        eng = self.engine()
+        dev, win = eng.device, self.cfg.window
+        ln, rl = _upload(L, torch.int32, dev), _upload(R, torch.int32, dev)
+        rot = rot_in.to(dev).float().reshape(B, Lmax, 9).contiguous()
+        trans = trans_in.to(dev).float().contiguous()
+        ref = gt.to(dev).double().contiguous()
+        src = pred_scale if pred_scale is not None else data["aligned_scale"]
+        scale = torch.as_tensor(src).to(dev).double().reshape(-1).expand(B).contiguous()
+        feats = torch.empty(B, win, 18, device=dev)
+        valid = torch.empty(B, dtype=torch.int32, device=dev)
+        Rn = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
+        Ral = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
+        pose = torch.zeros(B, Lmax, 7, dtype=torch.float64, device=dev)
+        origin = ref[:, 0, :3].contiguous()
+        with torch.cuda.device(eng.dev_index):
+            _lib.check_s1(eng.lib.egoego_s1_gravity_features(rot.data_ptr(), trans.data_ptr(), ln.data_ptr(), B, Lmax, win,
+                                                             feats.data_ptr(), valid.data_ptr(), eng._stream()))
+        normal = eng.encode(feats, valid)
+        with torch.cuda.device(eng.dev_index):
+            _lib.check_s1(eng.lib.egoego_s1_gravity_align(rot.data_ptr(), trans.data_ptr(), ln.data_ptr(), B, Lmax, normal.data_ptr(),
+                                                          scale.data_ptr(), ref.data_ptr(), rl.data_ptr(), Rmax, Rn.data_ptr(),
+                                                          Ral.data_ptr(), eng._stream()))
+            _lib.check_s1(eng.lib.egoego_s1_gravity_apply(rot.data_ptr(), trans.data_ptr(), ln.data_ptr(), B, Lmax, Rn.data_ptr(),
+                                                          scale.data_ptr(), Ral.data_ptr(), origin.data_ptr(), pose.data_ptr(),
+                                                          eng._stream()))
+        n_l, n_r = ln.long(), rl.long()
+        out = defaultdict(list)
+        out["head_trans"] = pose[..., :3]
+        out["head_rot_mat"] = _keep_rows(rotations.quaternion_to_matrix(pose[..., 3:]), n_l)
+        out["head_pose"] = pose
+        out["gt_head_trans"] = _keep_rows(ref[..., :3], n_r)
+        out["gt_head_rot_mat"] = _keep_rows(rotations.quaternion_to_matrix(ref[..., 3:]), n_r)
+        out["gt_head_pose"] = _keep_rows(torch.cat((ref[..., :3], rotations.matrix_to_quaternion(out["gt_head_rot_mat"])), -1), n_r)
+        out["pred_normal"] = normal
+        out["normal_rot"] = Rn
+        out["align_rot"] = Ral
+        out["lengths"] = torch.tensor(L, dtype=torch.int64)
+        out["ref_lengths"] = torch.tensor(R, dtype=torch.int64)
+        return out
 
-def estimate_head_pose(headnet, gravitynet, batch, z_offset=-0.13):
+
+def stage1_ragged(headnet, gravitynet, batch, lengths, pose_lengths=None):
+    """Both estimators on B sequences of different lengths (forward_for_eval(..., lengths=) of each, GravityNet on HeadNet's
+    pred_scale) -> (GravityNet's translation with HeadNet's rotation [B, Nmax, 7] float64, unmasked past each end; HeadNet's
+    output; GravityNet's output; the valid frames n_b = min(L_b, T_b + 1) as a host list)."""
+    out = headnet.forward_for_eval(batch, lengths=lengths, pose_lengths=pose_lengths)
+    L = pose_lengths if pose_lengths is not None else [int(t) + 1 for t in torch.as_tensor(lengths).reshape(-1).tolist()]
+    ori = torch.as_tensor(batch["ori_slam_trans"])
+    normal_in = {"head_trans": ori - ori[:, 0:1, :], "head_rot_mat": torch.as_tensor(batch["ori_slam_rot_mat"]),
+                 "ori_head_pose": torch.as_tensor(batch["head_pose"])}
+    nout = gravitynet.forward_for_eval(normal_in, out["pred_scale"], lengths=L, ref_lengths=L)
+    n = out["lengths"].tolist()
+    N = max(n)
+    hp = torch.cat((nout["head_pose"][:, :N, :3], out["head_pose"][:, :N, 3:].to(nout["head_pose"].device)), -1).double()
+    return hp, out, nout, n
+
+
+def estimate_head_pose(headnet, gravitynet, batch, z_offset=-0.13, lengths=None, pose_lengths=None):
     """RE:104-136: HeadNet's rotations with GravityNet's translation, moved onto the ground-truth start and shifted by z_offset
     (the reference's -0.13, "only for this sequence") -> [B, T, 7] float64 (xyz, quaternion w,x,y,z), what stage 2 takes.
-    Also returns the two estimators' outputs."""
+    Also returns the two estimators' outputs.
+
+    With `lengths` (feature frames per sequence; pose_lengths defaults to lengths + 1) the batch is padded and the sequences
+    differ in length: -> (poses [B, max n_b, 7], zero past n_b; the two outputs; the lengths n_b = min(L_b, T_b + 1), a CPU
+    tensor), what full_body_gen_cond_head_pose_sliding_window_ragged takes as head_poses and lengths."""
+    if lengths is not None:
+        hp, out, nout, n = stage1_ragged(headnet, gravitynet, batch, lengths, pose_lengths)
+        hp[:, :, :2] -= hp[:, 0:1, :2].clone()
+        gt0 = torch.as_tensor(batch["head_pose"])[:, 0:1, :3].to(hp.device).double()
+        hp[:, :, :3] += gt0 - hp[:, 0:1, :3]
+        hp[:, :, 2] += z_offset
+        return _keep_rows(hp, _upload(n, torch.int64, hp.device)), out, nout, out["lengths"]
+    if pose_lengths is not None:
+        raise ValueError("pose_lengths needs lengths")
     out = headnet.forward_for_eval(batch)
     ori = torch.as_tensor(batch["ori_slam_trans"])
     normal_in = {"head_trans": ori - ori[:, 0:1, :], "head_rot_mat": torch.as_tensor(batch["ori_slam_rot_mat"]),
@@ -583,6 +757,51 @@ def estimate_head_pose(headnet, gravitynet, batch, z_offset=-0.13):
     hp[:, :, :3] += gt0 - hp[:, 0:1, :3]
     hp[:, :, 2] += z_offset
     return hp, out, nout
+
+
+# ------------------------------------------------------------------------------------------ the stage-1 score
+def head_pose_metrics(pred_pose, gt_pose, lengths=None):
+    """egoego/eval/head_pose_metrics.py compute_head_pose_metrics on poses [B, T, 7] (xyz + quaternion w,x,y,z) on the device ->
+    float64 [B, 3] = (head_dist, head_dist_rot_only, head_trans_err in mm) over the first lengths[b] frames (None: all T)."""
+    p, g = torch.as_tensor(pred_pose), torch.as_tensor(gt_pose)
+    if p.dim() != 3 or p.shape[-1] != 7 or g.shape != p.shape or p.shape[0] < 1 or p.shape[1] < 1:
+        raise ValueError(f"poses {tuple(p.shape)} / {tuple(g.shape)}: two [B, T, 7] tensors expected")
+    if p.device.type != "cuda" or g.device != p.device:
+        raise _lib.EgoEgoHipError("the head-pose metrics need tensors on one cuda (ROCm) device; there is no CPU path")
+    dev = p.device
+    B, T = p.shape[:2]
+    if lengths is None:
+        ln = torch.full((B,), T, dtype=torch.int32, device=dev)
+    elif isinstance(lengths, torch.Tensor) and lengths.device.type == "cuda":
+        ln = lengths.to(dev, torch.int32).reshape(-1).contiguous()  # taken as given: the kernel clamps it to 0..T
+        if ln.shape != (B,):
+            raise ValueError(f"lengths {tuple(lengths.shape)}: [{B}] expected")
+    else:
+        ln = _upload(_host_lengths(lengths, B, T, "lengths"), torch.int32, dev)
+    p, g = p.double().contiguous(), g.double().contiguous()
+    out = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check_s1(_lib.load().egoego_s1_head_pose_metrics(p.data_ptr(), g.data_ptr(), ln.data_ptr(), B, T, out.data_ptr(), stream))
+    return out
+
+
+def compute_head_pose_metrics(head_trans, head_rot, gt_head_trans, gt_head_rot, lengths=None):
+    """The reference's compute_head_pose_metrics (same argument order) on the device: translations [T, 3] or [B, T, 3], rotation
+    matrices [T, 3, 3] or [B, T, 3, 3] (converted to quaternions on the device in float64) -> (head_dist, head_dist_rot_only,
+    head_trans_err in mm), three float64 [B] tensors.  lengths [B]: the valid frames of each sequence (None: all T)."""
+    ts = [torch.as_tensor(t) for t in (head_trans, head_rot, gt_head_trans, gt_head_rot)]
+    if ts[0].dim() == 2:
+        ts = [t[None] for t in ts]
+    pt, pr, gt, gr = ts
+    if pt.dim() != 3 or pt.shape[-1] != 3 or pr.shape != pt.shape[:2] + (3, 3) or gt.shape != pt.shape or gr.shape != pr.shape:
+        raise ValueError(f"head_trans {tuple(pt.shape)}, head_rot {tuple(pr.shape)}, gt_head_trans {tuple(gt.shape)}, gt_head_rot "
+                         f"{tuple(gr.shape)}: [B, T, 3] and [B, T, 3, 3] (or without B) expected")
+    if any(t.device.type != "cuda" for t in ts):
+        raise _lib.EgoEgoHipError("the head-pose metrics need tensors on a cuda (ROCm) device; there is no CPU path")
+    pose = lambda t, r: torch.cat((t.double(), rotations.matrix_to_quaternion(r.double())), -1)  # noqa: E731
+    m = head_pose_metrics(pose(pt, pr), pose(gt, gr), lengths)
+    return m[:, 0], m[:, 1], m[:, 2]
 
 
 # ------------------------------------------------------------------------------------------ the ARES demo sequence (AD)

@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*), the motion windows (egoego_win_*), the ragged sampling entry points (egoego_*_ragged) the AMASS preprocessing (egoego_amass_*) and the stage-2 training step (egoego_train_*) were added under 8: purely additive, no existing entry changed */
+#define EGOEGO_ABI_VERSION 8 /* 5: EGOEGO_FLAG_FC24; 6: EGOEGO_FLAG_FFN16; 7: stage 1 (egoego_s1_*); 8: flow CNN (egoego_flow_*); the body model (egoego_body_*), the evaluation (egoego_eval_*), the motion windows (egoego_win_*), the ragged sampling entry points (egoego_*_ragged) the AMASS preprocessing (egoego_amass_*) the stage-2 training step (egoego_train_*) and stage 1's alignment and score (egoego_s1_gravity_align, egoego_s1_head_pose_metrics) were added under 8: purely additive, no existing entry changed */
 
 enum {
     EGOEGO_OK = 0,
@@ -398,6 +398,31 @@ int egoego_s1_integrate(const float* d_heads, int window, const int32_t* d_T, co
  * with w >= 0.  d_rot / d_trans / d_len as for egoego_s1_gravity_features; Rn, Ralign [S][3][3], scale [S], origin [S][3]. */
 int egoego_s1_gravity_apply(const float* d_rot, const float* d_trans, const int32_t* d_len, int S, int Lmax, const double* d_Rn,
                             const double* d_scale, const double* d_Ralign, const double* d_origin, double* d_pose, void* stream);
+
+/* The two 3 x 3 steps between GravityNet's normal and egoego_s1_gravity_apply (HN:47-63 and evo's Umeyama alignment, HN:230-270),
+ * fp64, one workgroup per sequence; no context, no workspace.  d_rot is not read (the alignment sees positions only) and may be
+ * NULL; d_trans / d_len as for egoego_s1_gravity_apply; d_normal [S][3] fp32 (egoego_s1_encode's GravityNet output); d_scale [S];
+ * d_ref [S][Rmax][7] fp64 (xyz + quaternion, only xy is read) with d_ref_len int32 [S].
+ *   d_Rn [S][3][3]      the Rodrigues rotation taking the normal onto +z, rounded through fp32 (a normal parallel to z divides by
+ *                       zero, as the reference's formula does)
+ *   d_Ralign [S][3][3]  evo's Umeyama rotation of est_i = p_0 + sum_{k<=i} scale Rn (p_k - p_{k-1}) onto ref_i over the first
+ *                       n = min(len, ref_len) frames with z set to 1, rounded through fp32: blockdiag(Q, det Q), Q the orthogonal
+ *                       polar factor of the 2 x 2 covariance (closed form, no SVD).  Identity when the covariance is zero (n <= 1).
+ *                       On a straight line (rank-1 covariance) the reference's own answer is arbitrary between the rotation and the
+ *                       z-flipping reflection; the result is then only promised finite, orthonormal, det +1.
+ * The frames are summed in a fixed order (serial chain, per-lane fp64 partials folded in lane order): a sequence's result does not
+ * depend on the batch around it or on Lmax / Rmax. */
+int egoego_s1_gravity_align(const float* d_rot, const float* d_trans, const int32_t* d_len, int S, int Lmax, const float* d_normal,
+                            const double* d_scale, const double* d_ref, const int32_t* d_ref_len, int Rmax, double* d_Rn,
+                            double* d_Ralign, void* stream);
+
+/* egoego/eval/head_pose_metrics.py compute_head_pose_metrics for B sequences, fp64, one workgroup per sequence; no context, no
+ * workspace.  d_pred / d_gt [B][Tmax][7] fp64 (xyz + quaternion w,x,y,z, converted by pytorch3d's quaternion_to_matrix formula),
+ * d_lengths int32 [B] (1..Tmax; frames past it are never read) -> d_out [B][3] = (head_dist, head_dist_rot_only, head_trans_err
+ * in mm), each a per-frame sum in a fixed order divided by the length.  With E = Rp Rg^-1 (3 x 3 inverse by adjugate):
+ * head_dist = sqrt(|I - E|_F^2 + |tp - E tg|^2) (= |I4 - X Y^-1|_F), head_dist_rot_only = |I3 - E|_F, head_trans_err = |tp - tg|. */
+int egoego_s1_head_pose_metrics(const double* d_pred, const double* d_gt, const int32_t* d_lengths, int B, int Tmax, double* d_out,
+                                void* stream);
 
 /* ==================================================================================================================
  * Stage 1's optical-flow feature extractor: FeatureExtractor (egoego/model/resnet.py = RN, lines 25-50), i.e. torchvision's
