@@ -74,6 +74,24 @@ class BodyModelDesc(C.Structure):
         (n, C.c_void_p) for n in ("v_template", "shapedirs", "posedirs", "j_template", "j_shapedirs", "skin_weight", "skin_joint",
                                   "parents")]
 
+
+
+class OptimState(C.Structure):
+    """egoego_optim_state: the head of the fused update's state block"""
+    _fields_ = [("adam_step", C.c_int64), ("applied", C.c_int64), ("skipped", C.c_int64), ("total_norm", C.c_double),
+                ("total_norm_f32", C.c_float), ("last_skip", C.c_int32), ("step_size", C.c_float), ("bc2_sqrt", C.c_float),
+                ("one_minus_decay", C.c_float), ("ema_action", C.c_int32)]
+
+
+class OptimHyper(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
+class OptimEma(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("beta", "inv_gamma", "power", "min_value")] + [
+        ("update_every", C.c_int64), ("update_after_step", C.c_int64), ("d_step", C.c_void_p), ("d_initted", C.c_void_p)]
+
+
 EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoego_ctx_destroy",
            "egoego_load_weights", "egoego_load_schedule", "egoego_workspace_bytes", "egoego_denoise",
            "egoego_p_sample", "egoego_sample_loop", "egoego_denoise_ragged", "egoego_p_sample_ragged", "egoego_sample_loop_ragged",
@@ -92,12 +110,18 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_amass_last_error", "egoego_amass_max_frames", "egoego_amass_joints", "egoego_amass_floor_workspace_bytes",
            "egoego_amass_floor_contacts", "egoego_amass_head",
            "egoego_train_last_error", "egoego_train_ctx_create", "egoego_train_ctx_destroy", "egoego_train_workspace_bytes",
-           "egoego_train_saves_bytes", "egoego_train_forward", "egoego_train_backward", "egoego_train_dropout_mask", "egoego_train_saved"]
+           "egoego_train_saves_bytes", "egoego_train_forward", "egoego_train_backward", "egoego_train_dropout_mask", "egoego_train_saved",
+           "egoego_optim_last_error", "egoego_optim_ctx_create", "egoego_optim_ctx_destroy", "egoego_optim_workspace_bytes",
+           "egoego_optim_state_bytes", "egoego_optim_set_tensors", "egoego_optim_step", "egoego_optim_read_state"]
 LOSS_L1, LOSS_L2 = 0, 1
 TRAIN_SITE_ATTN, TRAIN_SITE_FC, TRAIN_SITE_FFN = 0, 1, 2
 TRAIN_SAVED = {"ffn_hidden": 0, "attn_prob": 1, "attn_out": 2, "attn_ln": 3, "layer_out": 4, "layer_in": 5}
 TRAIN_MAX_L = 197        # the longest window + 1 the training step accepts
 TRAIN_GRAD_CHUNK = 512   # rows per partial of a weight / bias gradient sum (csrc/train_step.h)
+OPTIM_CHUNK = 4096       # elements per chunk of the fused parameter update (csrc/optim_step.h)
+OPTIM_MAX_LOSSES = 8
+OPTIM_SKIP = {"nan": 0, "nonfinite": 1}
+OPTIM_EMA_NONE, OPTIM_EMA_COPY, OPTIM_EMA_LERP = 0, 1, 2
 EVAL_METRIC_KEYS = ("root_dist", "root_rot_dist", "root_trans_dist", "head_dist", "head_rot_dist", "head_trans_dist", "mpjpe",
                     "mpjpe_wo_hand", "accel_pred", "accel_gt", "accel_err", "pred_fs", "gt_fs")  # then single_jpe[22]
 EVAL_N_METRICS = len(EVAL_METRIC_KEYS) + 22
@@ -228,6 +252,21 @@ def load():
     lib.egoego_train_backward.argtypes = [vp, C.POINTER(Weights), vp, sz, vp, C.POINTER(Weights), C.c_float, u64, i32, i32, vp, sz, vp]
     lib.egoego_train_dropout_mask.argtypes = [vp, C.c_float, u64, i32, i32, vp, i32, i32, vp, vp, sz, vp]
     lib.egoego_train_saved.argtypes = [vp, vp, sz, i32, i32, i32, i32, vp, vp]
+    lib.egoego_optim_last_error.restype = C.c_char_p
+    lib.egoego_optim_ctx_create.argtypes = [i32, i32, C.POINTER(i64), C.POINTER(vp)]
+    lib.egoego_optim_ctx_destroy.argtypes = [vp]
+    lib.egoego_optim_ctx_destroy.restype = None
+    lib.egoego_optim_workspace_bytes.argtypes = [vp]
+    lib.egoego_optim_workspace_bytes.restype = sz
+    lib.egoego_optim_state_bytes.argtypes = [vp]
+    lib.egoego_optim_state_bytes.restype = sz
+    # ctx, p, g, m, v, ema (host arrays of device pointers; g, m, v / ema may be NULL), state, bytes, stream
+    lib.egoego_optim_set_tensors.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, sz, vp]
+    # ctx, hyper, ema, losses (host array of device pointers), n_losses, inv_scale, found_inf, skip_on, zero_grads, do_adam, do_ema,
+    # state, bytes, workspace, bytes, stream
+    lib.egoego_optim_step.argtypes = [vp, C.POINTER(OptimHyper), C.POINTER(OptimEma), C.POINTER(vp), i32, vp, vp, i32, i32, i32, i32,
+                                      vp, sz, vp, sz, vp]
+    lib.egoego_optim_read_state.argtypes = [vp, vp, sz, vp, vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -256,3 +295,4 @@ check_eval = _checker("evaluation ", "egoego_eval_last_error")
 check_win = _checker("motion-window ", "egoego_win_last_error")
 check_amass = _checker("AMASS-preprocessing ", "egoego_amass_last_error")
 check_train = _checker("training-step ", "egoego_train_last_error")
+check_optim = _checker("parameter-update ", "egoego_optim_last_error")

@@ -1,0 +1,158 @@
+"""The stage-2 training loop: the reference's Trainer.train() (trainer_amass_cond_motion_diffusion.py:124-205) without wandb and
+visualisation, over the fused parameter update of optim.py.
+
+    trainer = Stage2Trainer(model, DataLoader(MotionWindowDataset(windows, stats), batch_size=32, shuffle=True),
+                            results_folder="weights", fused=True, host_check=50)
+    trainer.train(10000)          # -> model-<milestone>.pt with the reference's keys {'step', 'model', 'ema', 'scaler'}
+"""
+import os
+
+import torch
+
+from . import harness
+from .optim import EMA, FusedAdam
+from .synthetic import head_condition_mask
+
+
+def cycle(dl):
+    while True:
+        for data in dl:
+            yield data
+
+
+class Stage2Trainer:
+    """Gradient accumulation, the NaN skip, Adam, the EMA and the checkpoints of the reference's Trainer.
+
+    NaN handling is the reference's end state: an iteration with a NaN loss or a NaN gradient norm in any micro-batch changes
+    nothing and does not advance `step`.  The reference checks after every backward; a NaN planted by one micro-batch survives
+    accumulation, so ONE norm check on the accumulated gradients, together with the micro-batches' loss scalars, decides the same
+    iterations.  The decision is taken on the device (optim.FusedAdam.step(losses=...)).
+
+    host_check=1 reads the skip flag back every iteration: `self.step` and the save cadence are exactly the reference's.
+    host_check=N reads the counters every N iterations only — no synchronisation in between — and sets `self.step` from the
+    applied count then: the checkpoint of a milestone may be written up to N - 1 iterations late (with the weights of that later
+    iteration), and `self.step` is only current right after a check or after train() returns.
+
+    fused=False is the plain path (torch.optim.Adam, ema-pytorch's lerp; any device); it decides on the host every iteration."""
+
+    def __init__(self, model, train_batches, val_batches=None, *, ema_decay=0.995, train_lr=1e-4, gradient_accumulate_every=2,
+                 amp=False, ema_update_every=10, save_and_sample_every=200000, results_folder="./results", fused=True, host_check=1,
+                 save_optimizer=False, ema_kwargs=None):
+        if host_check < 1:
+            raise ValueError("host_check >= 1")
+        if gradient_accumulate_every < 1 or gradient_accumulate_every > 8:
+            raise ValueError("gradient_accumulate_every: 1 .. 8 (the update takes up to 8 loss scalars)")
+        self.model = model
+        self.fused = bool(fused)
+        self.ema = EMA(model, beta=ema_decay, update_every=ema_update_every, fused=self.fused, **(ema_kwargs or {}))
+        self.save_and_sample_every = int(save_and_sample_every)
+        self.gradient_accumulate_every = int(gradient_accumulate_every)
+        self.optimizer = FusedAdam(model.parameters(), lr=train_lr, fused=self.fused, modules=(model,), zero_grads=self.fused)
+        self.step = 0
+        self.amp = bool(amp)
+        dev = next(model.parameters()).device
+        self.scaler = torch.amp.GradScaler(dev.type, enabled=self.amp)
+        self.results_folder = results_folder
+        self.save_optimizer = bool(save_optimizer)
+        self.host_check = 1 if not self.fused else int(host_check)
+        self.window = int(model.seq_len)
+        self.dl = cycle(train_batches)
+        self.val_dl = None if val_batches is None else cycle(val_batches)
+        self.last_losses = None
+        self._saved = 0      # the last milestone written
+        self._base = 0       # self.step minus the optimizer's applied count (a loaded checkpoint starts above 0)
+        self.inject_loss = None  # tests: f(iteration, micro-batch, loss) -> loss
+
+    # ------------------------------------------------------------------ checkpoints (trainer:99-122)
+    def _path(self, milestone):
+        return os.path.join(self.results_folder, "model-" + str(milestone) + ".pt")
+
+    def save(self, milestone):
+        data = {"step": self.step, "model": self.model.state_dict(), "ema": self.ema.state_dict(), "scaler": self.scaler.state_dict()}
+        if self.save_optimizer:
+            data["optimizer"] = self.optimizer.state_dict()
+        os.makedirs(self.results_folder, exist_ok=True)
+        torch.save(data, self._path(milestone))
+
+    def load(self, milestone):
+        self.load_weight_path(self._path(milestone))
+
+    def load_weight_path(self, weight_path):
+        data = torch.load(weight_path, map_location=next(self.model.parameters()).device)
+        self.step = int(data["step"])
+        self.model.load_state_dict(data["model"], strict=False)
+        self.ema.load_state_dict(data["ema"], strict=False)
+        self.scaler.load_state_dict(data["scaler"])
+        if "optimizer" in data:
+            self.optimizer.load_state_dict(data["optimizer"])
+        for m in (self.model, self.ema.ema_model):
+            if hasattr(m, "invalidate_engine"):
+                m.invalidate_engine()
+        self._base = self.step - self.optimizer.counters()["applied"]
+        self._saved = self.step // self.save_and_sample_every
+
+    # ------------------------------------------------------------------ the loop (trainer:124-205)
+    def prep_padding_mask(self, data, seq_len):
+        return harness.prep_padding_mask(data, torch.as_tensor(seq_len), self.window)
+
+    def prep_head_condition_mask(self, data):
+        return head_condition_mask(tuple(data.shape), device=data.device)
+
+    def _sync_step(self):
+        """host_check > 1: self.step from the device's applied count (one synchronisation)."""
+        self.step = self._base + int(self.optimizer.counters()["applied"])
+
+    def _iteration(self, idx):
+        """One iteration: the micro-batches, then the update.  -> whether the host knows the step was applied (None: not read)."""
+        dev = next(self.model.parameters()).device
+        self.optimizer.zero_grad()
+        losses = []
+        for i in range(self.gradient_accumulate_every):
+            batch = next(self.dl)
+            data = batch["motion"].to(dev)
+            padding_mask = self.prep_padding_mask(data, batch["seq_len"])
+            with torch.autocast(dev.type, enabled=self.amp):
+                cond_mask = self.prep_head_condition_mask(data)
+                loss = self.model(data, cond_mask, padding_mask=padding_mask)
+                if self.inject_loss is not None:
+                    loss = self.inject_loss(idx, i, loss)
+                self.scaler.scale(loss / self.gradient_accumulate_every).backward()
+            losses.append(loss.detach())
+        self.last_losses = losses
+        # with amp on, a skipped iteration goes through GradScaler.update() like any other (found_inf halves the scale); the
+        # reference leaves the scaler alone there.  amp off (the reference's default): both are no-ops.
+        self.scaler.step(self.optimizer, ema=self.ema, losses=losses)
+        self.scaler.update()
+        if self.host_check == 1:
+            return not bool(self.optimizer.last_skipped)
+        return None
+
+    def train(self, num_iterations):
+        """Runs `num_iterations` iterations of the reference's loop (a skipped iteration counts as one, as there) -> self.step."""
+        every = self.save_and_sample_every
+        for idx in range(num_iterations):
+            applied = self._iteration(idx)
+            if applied:  # host_check = 1: the reference's bookkeeping, line by line (trainer:181-203)
+                if self.step != 0 and self.step % every == 0:
+                    self._sample_and_save(self.step // every)
+                self.step += 1
+            elif applied is None and (idx + 1) % self.host_check == 0:
+                self._sync_step()
+                if self.step // every > self._saved:
+                    self._sample_and_save(self.step // every)
+        if self.host_check > 1:
+            self._sync_step()
+        return self.step
+
+    def _sample_and_save(self, milestone):
+        self._saved = milestone
+        if self.val_dl is not None:
+            self.ema.ema_model.eval()
+            with torch.no_grad():
+                dev = next(self.model.parameters()).device
+                val = next(self.val_dl)
+                val_data = val["motion"].to(dev)
+                cond_mask = self.prep_head_condition_mask(val_data)
+                padding_mask = self.prep_padding_mask(val_data, val["seq_len"])
+                self.last_sample = self.ema.ema_model.sample(val_data, cond_mask, padding_mask=padding_mask)
+        self.save(milestone)

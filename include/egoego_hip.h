@@ -697,6 +697,80 @@ int egoego_train_dropout_mask(egoego_train_ctx* ctx, float p_drop, uint64_t drop
 int egoego_train_saved(egoego_train_ctx* ctx, const void* d_saves, size_t saves_bytes, int B, int T, int layer, int which, float* d_out,
                        void* stream);
 
+/* ==================================================================================================================
+ * The fused parameter update (egoego_optim_*; added under ABI 8, purely additive): gradient norm, NaN skip, unscale, Adam
+ * (torch.optim.Adam, amsgrad off), ema-pytorch's EMA and gradient clearing over a list of fp32 contiguous device tensors, each with
+ * a gradient, exp_avg and exp_avg_sq of its own size and, optionally, an EMA tensor.  One step is three launches on `stream`:
+ * one partial sum of (g * inv_scale)^2 per chunk of EGOEGO_OPTIM_CHUNK elements (fp64, fixed order); one workgroup that adds the
+ * partials in a fixed order (thread t the partials of its run of consecutive chunks in chunk order, then the 256 sums in thread
+ * order), decides whether the step is skipped, advances the counters and writes this step's scalars, all in fp64 rounded once;
+ * and the update itself.  Nothing is read back: a skipped step (NaN norm, NaN loss, found_inf) writes no parameter, moment or EMA
+ * value, and the step counters stay.
+ *   - the caller allocates everything: the moments, the state block (egoego_optim_state_bytes, 256-byte aligned, zeroed before
+ *     the first use) and the workspace (egoego_optim_workspace_bytes).  The state block begins with an egoego_optim_state and
+ *     holds the descriptor tables (tensor -> pointers, chunk -> tensor, offset, count) behind it; together with the EMA's two
+ *     counters (device scalars of the caller, as ema-pytorch keeps them) it is the only memory that carries meaning from call to
+ *     call.  What the workspace holds on entry is irrelevant.
+ *   - a call only enqueues work on `stream`: no allocation, no copy through the host, no synchronisation, no float atomics.
+ *   - a tensor may start at any 4-byte offset: 16-byte accesses are used where all tensors of an entry share their 16-byte phase.
+ * egoego_optim_last_error() describes the last failure of an egoego_optim_* call.
+ * ================================================================================================================== */
+typedef struct egoego_optim_ctx egoego_optim_ctx;
+#define EGOEGO_OPTIM_CHUNK 4096
+#define EGOEGO_OPTIM_MAX_LOSSES 8
+enum { EGOEGO_OPTIM_SKIP_NAN = 0,         /* the reference's rule (trainer:144-160): NaN only */
+       EGOEGO_OPTIM_SKIP_NONFINITE = 1 }; /* +-inf as well */
+enum { EGOEGO_OPTIM_EMA_NONE = 0, EGOEGO_OPTIM_EMA_COPY = 1, EGOEGO_OPTIM_EMA_LERP = 2 };
+
+/* The head of the state block.  Counters first, then what the last call decided. */
+typedef struct {
+    int64_t adam_step;      /* applied Adam steps: the `step` of torch.optim.Adam's state */
+    int64_t applied;        /* calls that were not skipped */
+    int64_t skipped;        /* calls that were */
+    double total_norm;      /* sqrt(sum (g * inv_scale)^2) of the last call with do_adam */
+    float total_norm_f32;
+    int32_t last_skip;      /* 1: the last call was skipped */
+    float step_size;        /* lr / (1 - beta1^step) */
+    float bc2_sqrt;         /* sqrt(1 - beta2^step) */
+    float one_minus_decay;  /* of the last lerp */
+    int32_t ema_action;     /* EGOEGO_OPTIM_EMA_* of the last call */
+} egoego_optim_state;
+
+typedef struct {
+    double lr, beta1, beta2, eps, weight_decay;  /* weight_decay: torch's L2 form, g + weight_decay * p */
+} egoego_optim_hyper;
+
+/* ema-pytorch's schedule: a call with do_ema reads *d_step, adds one, and acts only when the value it read is a multiple of
+ * update_every: a copy up to update_after_step and, once, on the first call after it (which sets *d_initted = 1); afterwards
+ * ema -= (ema - p) * (1 - decay), decay = clamp(1 - (1 + e / inv_gamma)^-power, min_value, beta), e = step read - update_after_step. */
+typedef struct {
+    double beta, inv_gamma, power, min_value;
+    int64_t update_every, update_after_step;
+    int64_t* d_step;   /* device scalar */
+    float* d_initted;  /* device scalar: 0 or 1 */
+} egoego_optim_ema;
+
+const char* egoego_optim_last_error(void);
+/* counts: HOST array of n_tensors element counts (each >= 1). */
+int egoego_optim_ctx_create(int device, int n_tensors, const int64_t* counts, egoego_optim_ctx** out);
+void egoego_optim_ctx_destroy(egoego_optim_ctx* ctx);
+size_t egoego_optim_workspace_bytes(const egoego_optim_ctx* ctx);
+size_t egoego_optim_state_bytes(const egoego_optim_ctx* ctx);
+/* Writes the descriptor tables of d_state from HOST arrays of n_tensors device pointers each: the parameters; gradients, exp_avg
+ * and exp_avg_sq (all three NULL for a context that only ever runs do_adam = 0); the EMA tensors or NULL.  Call it once, and again
+ * whenever one of the pointers has changed.  The counters of d_state are not touched. */
+int egoego_optim_set_tensors(egoego_optim_ctx* ctx, float* const* p, float* const* g, float* const* m, float* const* v, float* const* ema,
+                             void* d_state, size_t state_bytes, void* stream);
+/* One step.  losses: HOST array of n_losses (<= 8) pointers to device scalars, or NULL; d_inv_scale, d_found_inf: device scalars
+ * or NULL; do_adam = 0 runs the EMA alone (no norm, no moments); do_ema needs the EMA pointers of egoego_optim_set_tensors and
+ * ema->d_step / d_initted; zero_grads needs do_adam and clears the gradients whether the step is skipped or not. */
+int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, const egoego_optim_ema* ema, const float* const* losses,
+                      int n_losses, const float* d_inv_scale, const float* d_found_inf, int skip_on, int zero_grads, int do_adam, int do_ema,
+                      void* d_state, size_t state_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Copies the egoego_optim_state at the head of d_state to d_out (device memory) on `stream`: the one call a caller may follow with
+ * a synchronisation, to read counters for tests and logging. */
+int egoego_optim_read_state(egoego_optim_ctx* ctx, const void* d_state, size_t state_bytes, egoego_optim_state* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
