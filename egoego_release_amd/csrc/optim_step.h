@@ -220,7 +220,9 @@ __device__ __forceinline__ void update(const Apply& a, const Scalars& s, float* 
             for (int k = 0; k < W; ++k) {
                 float gg = G[k] * s.inv;
                 if (a.wd != 0.f) gg = gg + a.wd * P[k];
-                M[k] = M[k] + a.w1 * (gg - M[k]);
+                // torch's lerp_(grad, 1 - beta1): the weight decides the form, and a weight of 1 (beta1 = 0) returns gg itself
+                const float dm = gg - M[k];
+                M[k] = a.w1 < 0.5f ? M[k] + a.w1 * dm : gg - dm * (1.0f - a.w1);
                 const float vb = V[k] * a.beta2;
                 const float g2 = a.w2 * gg;
                 V[k] = vb + g2 * gg;

@@ -328,8 +328,12 @@ class EMA(nn.Module):
         self.online_model = model
         self.ema_model = copy.deepcopy(model) if ema_model is None else ema_model
         self.ema_model.requires_grad_(False)
-        self.register_buffer("initted", torch.Tensor([False]))
-        self.register_buffer("step", torch.tensor([0]))
+        # the HIP path keeps both counters beside the parameters from the start: moved there by the first update instead, that
+        # copy from host memory would be a synchronisation inside a training step
+        dev = next(model.parameters()).device if self.hip else torch.device("cpu")
+        dev = dev if dev.type == "cuda" else torch.device("cpu")
+        self.register_buffer("initted", torch.Tensor([False]).to(dev))
+        self.register_buffer("step", torch.tensor([0]).to(dev))
         self._engine = None
 
     def _pairs(self):

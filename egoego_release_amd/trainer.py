@@ -31,9 +31,12 @@ class Stage2Trainer:
     host_check=1 reads the skip flag back every iteration: `self.step` and the save cadence are exactly the reference's.
     host_check=N reads the counters every N iterations only — no synchronisation in between — and sets `self.step` from the
     applied count then: the checkpoint of a milestone may be written up to N - 1 iterations late (with the weights of that later
-    iteration), and `self.step` is only current right after a check or after train() returns.
+    iteration), and `self.step` is only current right after a check or after train() returns.  A check writes one checkpoint, that
+    of the latest milestone reached, so with fused=True save_and_sample_every must be at least host_check: a smaller value would
+    let several milestones pass between two checks and lose all but the last without a word; the constructor raises ValueError.
 
-    fused=False is the plain path (torch.optim.Adam, ema-pytorch's lerp; any device); it decides on the host every iteration."""
+    fused=False is the plain path (torch.optim.Adam, ema-pytorch's lerp; any device); it decides on the host every iteration
+    (host_check is taken as 1)."""
 
     def __init__(self, model, train_batches, val_batches=None, *, ema_decay=0.995, train_lr=1e-4, gradient_accumulate_every=2,
                  amp=False, ema_update_every=10, save_and_sample_every=200000, results_folder="./results", fused=True, host_check=1,
@@ -42,6 +45,10 @@ class Stage2Trainer:
             raise ValueError("host_check >= 1")
         if gradient_accumulate_every < 1 or gradient_accumulate_every > 8:
             raise ValueError("gradient_accumulate_every: 1 .. 8 (the update takes up to 8 loss scalars)")
+        if fused and int(save_and_sample_every) < int(host_check):
+            raise ValueError(f"save_and_sample_every = {save_and_sample_every} is below host_check = {host_check}: the host learns the step "
+                             "count every host_check iterations and writes one checkpoint then, so the milestones in between would "
+                             "never be written; check at least as often as you save")
         self.model = model
         self.fused = bool(fused)
         self.ema = EMA(model, beta=ema_decay, update_every=ema_update_every, fused=self.fused, **(ema_kwargs or {}))

@@ -88,11 +88,16 @@ def step(p, g, m, v, ema, c, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay
     return P, M, V, E, n, info
 
 
-def ulp_distance(got, want64):
-    """The largest |got - want| in units of the fp32 ulp of `want` (want: fp64; its ulp is that of its fp32 rounding; values below
-    the smallest normal count in units of the smallest subnormal)."""
+def ulp_distances(got, want64):
+    """|got - want| element by element in units of the fp32 ulp of `want` (want: fp64; its ulp is that of its fp32 rounding; values
+    below the smallest normal count in units of the smallest subnormal)."""
     w = f64(want64)
     w32 = np.abs(w.astype(np.float32))
     ulp = f64(np.spacing(np.maximum(w32, np.float32(np.finfo(np.float32).tiny))))
-    d = np.abs(f64(got) - w) / ulp
+    return np.abs(f64(got) - w) / ulp
+
+
+def ulp_distance(got, want64):
+    """The largest of ulp_distances()."""
+    d = ulp_distances(got, want64)
     return float(d.max()) if d.size else 0.0

@@ -5,6 +5,8 @@ import importlib.util
 import inspect
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -150,6 +152,25 @@ def test_fused_adam_refuses_what_it_does_not_serve():
     assert list(inspect.signature(optim.FusedAdam.step).parameters)[1:] == ["closure", "ema", "losses"]
 
 
+def test_apply_kernel_on_the_host_under_sanitizers(tmp_path):
+    """csrc/optim_step.h compiled by the host compiler over tests/host_sim's stand-in for the HIP header, and apply_kernel run
+    thread after thread by a stand-alone program (tests/host_sim/apply_main.cpp) under AddressSanitizer and UBSan's alignment
+    check.  The device takes a 16-byte access off its boundary without a word and computes the same values, so a wrong scalar
+    head — (4 - phase) & 1, say — passes every comparison there; here it stops the program, and so does an access over either
+    end of a view.  Every 16-byte phase, every single tensor off the others' phase, counts below the head and over two chunks;
+    every element visited exactly once under a grid smaller than the chunk count."""
+    sim = os.path.join(ROOT, "tests", "host_sim")
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler"
+    exe = str(tmp_path / "apply_sim")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=on", "-fsanitize=address,alignment", "-fno-sanitize-recover=all", "-I", sim, "-I", CSRC,
+           os.path.join(sim, "apply_main.cpp"), "-o", exe]
+    built = subprocess.run(cmd, capture_output=True, text=True)
+    assert built.returncode == 0, built.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert run.returncode == 0 and "24 cases, 0 wrong elements" in run.stdout, run.stdout + run.stderr
+
+
 # ---------------------------------------------------------------------------------------------------------------- the EMA schedule
 def test_ema_schedule_at_its_regime_changes():
     """update_every = 10, update_after_step = 100 (the reference's): the counter values 0, 1, 10; 100 and the first multiple after
@@ -239,6 +260,21 @@ def test_trainer_nan_loss_changes_nothing(tmp_path):
     assert tr.optimizer.counters()["skipped"] == 1 and int(tr.optimizer.last_skipped) == 1
     tr.inject_loss = None
     assert tr.train(1) == 3
+
+
+def test_trainer_refuses_a_save_cadence_its_checks_cannot_keep(tmp_path):
+    """fused=True reads the step count every host_check iterations and writes one checkpoint per check: milestones closer together
+    than the checks would be lost, so the constructor (which launches nothing) raises.  The plain path checks every iteration."""
+    cfg, m = _tiny()
+    kw = dict(results_folder=str(tmp_path))
+    with pytest.raises(ValueError, match="save_and_sample_every.*host_check"):
+        Stage2Trainer(m, _batches(), fused=True, host_check=5, save_and_sample_every=3, **kw)
+    with pytest.raises(ValueError, match="milestones"):
+        Stage2Trainer(m, _batches(), fused=True, host_check=4, save_and_sample_every=3, **kw)
+    assert Stage2Trainer(m, _batches(), fused=True, host_check=3, save_and_sample_every=3, **kw).host_check == 3
+    assert Stage2Trainer(m, _batches(), fused=True, host_check=1, save_and_sample_every=1, **kw).host_check == 1
+    assert Stage2Trainer(m, _batches(), fused=False, host_check=5, save_and_sample_every=3, **kw).host_check == 1
+    assert "save_and_sample_every must be at least host_check" in " ".join(Stage2Trainer.__doc__.split())
 
 
 def test_two_micro_batches_equal_one_step_on_the_summed_gradient(tmp_path):
