@@ -4,7 +4,7 @@ Only the sampling hot path lives here: HIP kernels + C ABI in cs
 mirror of the reference's CondGaussianDiffusion interface in model.py.
 """
 from .synthetic import ModelConfig, make_weights, make_head_windows, head_condition_mask  # noqa: F401
-from .synthetic import Stage1Config, make_stage1_weights  # noqa: F401
+from .synthetic import Stage1Config, make_stage1_weights, make_stage1_train_batch  # noqa: F401
 from .synthetic import make_flow_cnn_weights, make_flows  # noqa: F401
 from .synthetic import make_body_model, make_body_poses  # noqa: F401
 from .synthetic import make_eval_motion  # noqa: F401

@@ -112,7 +112,11 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_train_last_error", "egoego_train_ctx_create", "egoego_train_ctx_destroy", "egoego_train_workspace_bytes",
            "egoego_train_saves_bytes", "egoego_train_forward", "egoego_train_backward", "egoego_train_dropout_mask", "egoego_train_saved",
            "egoego_optim_last_error", "egoego_optim_ctx_create", "egoego_optim_ctx_destroy", "egoego_optim_workspace_bytes",
-           "egoego_optim_state_bytes", "egoego_optim_set_tensors", "egoego_optim_step", "egoego_optim_read_state"]
+           "egoego_optim_state_bytes", "egoego_optim_set_tensors", "egoego_optim_step", "egoego_optim_read_state",
+           "egoego_s1_train_last_error", "egoego_s1_train_ctx_create", "egoego_s1_train_ctx_destroy", "egoego_s1_train_workspace_bytes",
+           "egoego_s1_train_saves_bytes", "egoego_s1_train_forward", "egoego_s1_train_backward", "egoego_s1_train_dropout_mask",
+           "egoego_s1_train_saved", "egoego_s1_headnet_loss_workspace_bytes", "egoego_s1_headnet_loss"]
+S1_TRAIN_SAVED = {"ffn_hidden": 0, "attn_prob": 1, "attn_out": 2, "attn_ln": 3, "layer_out": 4, "layer_in": 5, "head_hidden": 6}
 LOSS_L1, LOSS_L2 = 0, 1
 TRAIN_SITE_ATTN, TRAIN_SITE_FC, TRAIN_SITE_FFN = 0, 1, 2
 TRAIN_SAVED = {"ffn_hidden": 0, "attn_prob": 1, "attn_out": 2, "attn_ln": 3, "layer_out": 4, "layer_in": 5}
@@ -267,6 +271,24 @@ def load():
     lib.egoego_optim_step.argtypes = [vp, C.POINTER(OptimHyper), C.POINTER(OptimEma), C.POINTER(vp), i32, vp, vp, i32, i32, i32, i32,
                                       vp, sz, vp, sz, vp]
     lib.egoego_optim_read_state.argtypes = [vp, vp, sz, vp, vp]
+    lib.egoego_s1_train_last_error.restype = C.c_char_p
+    lib.egoego_s1_train_ctx_create.argtypes = [C.POINTER(S1Config), i32, C.POINTER(vp)]
+    lib.egoego_s1_train_ctx_destroy.argtypes = [vp]
+    lib.egoego_s1_train_ctx_destroy.restype = None
+    lib.egoego_s1_train_workspace_bytes.argtypes = [vp, i32]
+    lib.egoego_s1_train_workspace_bytes.restype = sz
+    lib.egoego_s1_train_saves_bytes.argtypes = [vp, i32]
+    lib.egoego_s1_train_saves_bytes.restype = sz
+    # ctx, weights, feats, valid, p_drop, seed, window ids, W, saves, bytes, workspace, bytes, heads, stream
+    lib.egoego_s1_train_forward.argtypes = [vp, C.POINTER(S1Weights), vp, vp, C.c_float, u64, vp, i32, vp, sz, vp, sz, vp, vp]
+    # ctx, weights, saves, bytes, d_heads, grads (the layout of S1Weights), p_drop, seed, W, workspace, bytes, stream
+    lib.egoego_s1_train_backward.argtypes = [vp, C.POINTER(S1Weights), vp, sz, vp, C.POINTER(S1Weights), C.c_float, u64, i32, vp, sz, vp]
+    lib.egoego_s1_train_dropout_mask.argtypes = [vp, C.c_float, u64, i32, i32, vp, i32, vp, vp, sz, vp]
+    lib.egoego_s1_train_saved.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp]
+    lib.egoego_s1_headnet_loss_workspace_bytes.argtypes = [i32]
+    lib.egoego_s1_headnet_loss_workspace_bytes.restype = sz
+    # heads, window, B, T, head_pose, head_vels, dist_scale, w_rotation, w_va, w_dist, loss, d_heads fp64, d_heads fp32, workspace, bytes, stream
+    lib.egoego_s1_headnet_loss.argtypes = [vp, i32, i32, i32, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, sz, vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -296,3 +318,4 @@ check_win = _checker("motion-window ", "egoego_win_last_error")
 check_amass = _checker("AMASS-preprocessing ", "egoego_amass_last_error")
 check_train = _checker("training-step ", "egoego_train_last_error")
 check_optim = _checker("parameter-update ", "egoego_optim_last_error")
+check_s1_train = _checker("stage-1 training ", "egoego_s1_train_last_error")

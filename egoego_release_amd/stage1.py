@@ -17,6 +17,9 @@ lengths in one call) both run in egoego_s1_gravity_align and nothing returns to 
 stage-1 score (egoego/eval/head_pose_metrics.py) on the device.  torch is plumbing only; there is no fallback.
 
 FlowFeatureExtractor turns raw optical flow into those features (RN's ResNet-18, egoego_flow_* in libegoego_hip).
+
+Training (opt-in): with `hip_training` set, forward() of either estimator runs the training encode of stage1_train.py and its
+outputs are connected to the parameters; compute_loss() is the reference's (HeadNet's on egoego_s1_headnet_loss).  DESIGN.md 5l.
 """
 import ctypes as C
 import os
@@ -215,14 +218,51 @@ class _Stage1Module(nn.Module):
             self.load_state_dict(make_stage1_weights(cfg.kind, cfg, 0))
         self._engine = None
         self._packed = None
+        self._train_engine = None
 
-    def _version(self):
+    # Opt-in: with hip_training set and grad mode on, forward() runs the training encode of csrc/stage1_train.* (stage1_train.py)
+    # and its outputs are connected to the parameters; off (the default), forward() is the inference encode, without a graph.
+    hip_training = False
+    P_DROP = 0.1  # TM's dropout at its three sites, in train() mode only
+
+    def _params_version(self):  # (not `_version`: nn.Module stores its state-dict format version under that name, and
+        # state_dict() would carry the bound method, and with it the whole module, into every checkpoint)
         return tuple((p.data_ptr(), p._version) for p in self.state_dict().values())
+
+    def train_engine(self):
+        """The training engine (egoego_s1_train_*), on the device of the parameters."""
+        from .stage1_train import Stage1TrainEngine
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise _lib.EgoEgoHipError("hip_training needs the module's parameters on a cuda (ROCm) device (module.to(device)); "
+                                      "there is no CPU path")
+        if self._train_engine is None or self._train_engine.device != torch.device("cuda", dev.index if dev.index is not None
+                                                                                  else torch.cuda.current_device()):
+            self._train_engine = Stage1TrainEngine(self.cfg, dev)
+        return self._train_engine
+
+    def _graph(self):
+        return bool(self.hip_training) and torch.is_grad_enabled()
+
+    def _exec_engine(self):
+        """The engine forward() runs on: the training engine while a graph is being built (it reads the live parameters, so an
+        optimizer step costs no re-pack), else the inference engine."""
+        return self.train_engine() if self._graph() else self.engine()
+
+    def _encode(self, feats, valid):
+        """The heads of W windows: the inference encode, or with hip_training and grad mode on the training encode (connected to
+        the parameters; dropout P_DROP with one host-drawn seed per call in train() mode, none in eval())."""
+        if not self._graph():
+            return self.engine().encode(feats, valid)
+        from .stage1_train import training_encode
+        p_drop = self.P_DROP if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0 else 0
+        return training_encode(self, self.train_engine(), feats, valid, p_drop, seed)
 
     def engine(self):
         if self._engine is None:
             self._engine = Stage1Engine(self.cfg, self.device)
-        v = self._version()
+        v = self._params_version()
         if v != self._packed:
             self._engine.load(self.state_dict())
             self._packed = v
@@ -262,7 +302,7 @@ class HeadFormer(_Stage1Module):
         ln = torch.full((B,), L, dtype=torch.int32, device=dev) if lens is None else torch.tensor(lens, dtype=torch.int32, device=dev)
         q0d = q0.to(dev, torch.float64).contiguous()
         sl = slam.to(dev, torch.float64).contiguous()
-        eng = self.engine()
+        eng = self._exec_engine()
         with torch.cuda.device(eng.dev_index):
             _lib.check_s1(eng.lib.egoego_s1_integrate(heads.data_ptr(), self.cfg.window, Tt.data_ptr(), w0.data_ptr(), q0d.data_ptr(),
                                                       sl.data_ptr(), ln.data_ptr(), B, L, Qmax, float(dist_scale), quat.data_ptr(),
@@ -270,8 +310,10 @@ class HeadFormer(_Stage1Module):
         return quat, trans, scale
 
     def forward(self, data):
-        """HE:123-170 on one window per sequence (T <= window tokens, data['seq_len'] valid)."""
-        eng = self.engine()
+        """HE:123-170 on one window per sequence (T <= window tokens, data['seq_len'] valid).  With hip_training set and grad mode
+        on, head_va and head_dist_scalar are connected to the parameters (the training encode); head_rot_quat is what it is
+        without the flag, integrated on the device and detached: the orientation term's gradient lives in compute_loss."""
+        eng = self._exec_engine()
         x = torch.as_tensor(data["of"]).to(eng.device).float()
         B, T, _ = x.shape
         if T > self.cfg.window:
@@ -279,15 +321,35 @@ class HeadFormer(_Stage1Module):
         feats = torch.zeros(B, self.cfg.window, self.cfg.d_feats, device=eng.device)
         feats[:, :T] = x
         valid = torch.as_tensor(data["seq_len"]).reshape(B).to(eng.device).to(torch.int32).clamp(0, T)
-        heads = eng.encode(feats, valid)
+        heads = self._encode(feats, valid)
         q0 = torch.as_tensor(data["head_pose"])[:, 0, 3:]
         slam = torch.zeros(B, 1, 3, dtype=torch.float64, device=eng.device)
-        quat, _, _ = self._integrate(heads, [T] * B, q0, slam, list(range(B)), 1.0)
+        quat, _, _ = self._integrate(heads.detach(), [T] * B, q0, slam, list(range(B)), 1.0)
         out = defaultdict(list)
         out["head_va"] = heads[:, :T, :3]
         out["head_rot_quat"] = quat.to(torch.as_tensor(data["head_pose"]).dtype)
         out["head_dist_scalar"] = heads[:, :T, 3:4]
         return out
+
+    def compute_loss(self, feature_pred, data):
+        """HE:310-345: -> (loss, orient_loss, va_loss, dist_loss) from feature_pred['head_va'] [B, T, 3] and
+        feature_pred['head_dist_scalar'] [B, T, 1] against data['head_pose'] [B, T + 1, 7] and data['head_vels'] [B, T, 6], with
+        opt.w_rotation, w_va, w_dist and dist_scale; every mean is over all B * T frames, padded ones included.  One call of
+        egoego_s1_headnet_loss (fp64 on the device).
+
+        The rotations are recomputed from head_va inside the kernel, and feature_pred['head_rot_quat'] is NOT read: va2rot
+        detaches the running rotation, so frame t's orientation term depends on head_va[:, t] alone, and the kernel returns that
+        gradient with the loss.  (The values agree with head_rot_quat: both integrate the same head_va from head_pose[:, 0].)
+        `loss` carries the gradient to head_va and head_dist_scalar; the three parts are reported values.  Works under no_grad
+        and with hip_training off (validation).  CPU tensors raise: there is no CPU path."""
+        from .stage1_train import HipHeadNetLoss
+        va, dist = feature_pred["head_va"], feature_pred["head_dist_scalar"]
+        if not isinstance(va, torch.Tensor) or va.device.type != "cuda" or dist.device != va.device:
+            raise _lib.EgoEgoHipError("compute_loss needs the predictions on a cuda (ROCm) device; there is no CPU path")
+        pose = torch.as_tensor(data["head_pose"]).to(va.device).float()
+        vels = torch.as_tensor(data["head_vels"]).to(va.device).float()
+        opt = self.opt
+        return HipHeadNetLoss.apply(va, dist, pose, vels, float(opt.dist_scale), float(opt.w_rotation), float(opt.w_va), float(opt.w_dist))
 
     def forward_for_eval(self, data, lengths=None, pose_lengths=None):
         """HE:214-308 for B sequences of equal length T at once: every block of every sequence in one encode call.
@@ -577,15 +639,16 @@ class HeadNormalFormer(_Stage1Module):
         self.transformer_window_size = cfg.window
 
     def _frames(self, data):
-        eng = self.engine()
+        eng = self._exec_engine()
         rot = torch.as_tensor(data["head_rot_mat"]).to(eng.device).float()
         trans = torch.as_tensor(data["head_trans"]).to(eng.device).float()
         B, L = rot.shape[:2]
         return rot.reshape(B, L, 9).contiguous(), trans.contiguous(), torch.full((B,), L, dtype=torch.int32, device=eng.device)
 
     def forward(self, data):
-        """HN:118-155: the floor normal of every sequence from its first window + 1 frames."""
-        eng = self.engine()
+        """HN:118-155: the floor normal of every sequence from its first window + 1 frames.  With hip_training set and grad mode
+        on, pred_normal is connected to the parameters (the training encode)."""
+        eng = self._exec_engine()
         rot, trans, ln = self._frames(data)
         B, L = rot.shape[:2]
         win = self.cfg.window
@@ -595,10 +658,21 @@ class HeadNormalFormer(_Stage1Module):
             _lib.check_s1(eng.lib.egoego_s1_gravity_features(rot.data_ptr(), trans.data_ptr(), ln.data_ptr(), B, L, win,
                                                              feats.data_ptr(), valid.data_ptr(), eng._stream()))
         out = defaultdict(list)
-        out["pred_normal"] = eng.encode(feats, valid)
+        out["pred_normal"] = self._encode(feats, valid)
         return out
 
-    def _apply(self, rot, trans, ln, Rn, scale, Ral, origin):
+    def compute_loss(self, feature_pred, data):
+        """HN:33-35, 334-342: -> (loss, normal_loss), |gt - pred| of the predicted floor normal against data['floor_normal']
+        ([B, 3] or [B, 3, 1]) summed over its 3 components, mean over B.  Three torch ops on the device (the training encode's
+        backward takes their gradient); works under no_grad and with hip_training off.  A CPU prediction raises."""
+        pred = feature_pred["pred_normal"]
+        if not isinstance(pred, torch.Tensor) or pred.device.type != "cuda":
+            raise _lib.EgoEgoHipError("compute_loss needs the prediction on a cuda (ROCm) device; there is no CPU path")
+        gt = torch.as_tensor(data["floor_normal"]).to(pred.device).squeeze(-1)
+        normal_loss = (gt - pred).abs().sum(dim=1).mean()
+        return normal_loss, normal_loss
+
+    def _apply_pose(self, rot, trans, ln, Rn, scale, Ral, origin):  # (not `_apply`: nn.Module moves its parameters through that name)
         eng = self.engine()
         B, L = rot.shape[:2]
         pose = torch.empty(B, L, 7, dtype=torch.float64, device=eng.device)
@@ -623,7 +697,8 @@ class HeadNormalFormer(_Stage1Module):
             return self._forward_for_eval_ragged(data, pred_scale, use_gt_aligned_rot, lengths, ref_lengths)
         if ref_lengths is not None:
             raise ValueError("ref_lengths needs lengths")
-        normal = self.forward(data)["pred_normal"]
+        with torch.no_grad():  # evaluation never builds a graph, whatever hip_training says
+            normal = self.forward(data)["pred_normal"]
         rot, trans, ln = self._frames(data)
         B, L = rot.shape[:2]
         if use_gt_aligned_rot:
@@ -636,7 +711,7 @@ class HeadNormalFormer(_Stage1Module):
             scale = torch.as_tensor(data["aligned_scale"]).double().reshape(-1).cpu().numpy()
         scale = np.array(np.broadcast_to(scale, (B,)))
         eye = np.tile(np.eye(3), (B, 1, 1))
-        est = self._apply(rot, trans, ln, Rn, scale, eye, trans[:, 0].double().cpu().numpy()).cpu().numpy()
+        est = self._apply_pose(rot, trans, ln, Rn, scale, eye, trans[:, 0].double().cpu().numpy()).cpu().numpy()
         ref = torch.as_tensor(data["ori_head_pose"]).double().cpu().numpy()
         Ral = np.empty((B, 3, 3))
         for b in range(B):
@@ -645,7 +720,7 @@ class HeadNormalFormer(_Stage1Module):
             r[:, 2] = 1
             Ral[b] = umeyama_rotation(e, r).astype(np.float32)
         gt = torch.as_tensor(data["ori_head_pose"])
-        pose = self._apply(rot, trans, ln, Rn, scale, Ral, gt[:, 0, :3].double().cpu().numpy())
+        pose = self._apply_pose(rot, trans, ln, Rn, scale, Ral, gt[:, 0, :3].double().cpu().numpy())
         out = defaultdict(list)
         out["head_trans"] = pose[..., :3]
         out["head_rot_mat"] = rotations.quaternion_to_matrix(pose[..., 3:])

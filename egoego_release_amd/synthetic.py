@@ -237,6 +237,93 @@ def make_stage1_weights(kind, cfg, seed=0):
     return sd
 
 
+def _np_qmul(a, b):
+    aw, ax, ay, az = np.moveaxis(a, -1, 0)
+    bw, bx, by, bz = np.moveaxis(b, -1, 0)
+    return np.stack((aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw), -1)
+
+
+def _np_aa2q(a):
+    ang = np.linalg.norm(a, axis=-1, keepdims=True)
+    s = np.where(ang < 1e-6, 0.5 - ang * ang / 48, np.sin(ang / 2) / np.maximum(ang, 1e-300))
+    return np.concatenate((np.cos(ang / 2), a * s), -1)
+
+
+def _np_q2mat(q):
+    w, x, y, z = np.moveaxis(q / np.linalg.norm(q, axis=-1, keepdims=True), -1, 0)
+    return np.stack((1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                     2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                     2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)), -1).reshape(q.shape[:-1] + (3, 3))
+
+
+def make_stage1_train_batch(kind, B, window, seed=0, lengths=None):
+    """A seeded reference-format training batch of a stage-1 estimator (what its DataLoader yields), for tests and benchmarks.
+
+    'headnet' (HE:131-178, 310-345): of [B, window, 512], head_pose [B, window + 1, 7] (xyz, unit quaternion w,x,y,z), head_vels
+    [B, window, 6] (linear | angular velocity), seq_len [B] (`lengths`, default window).  A smooth angular velocity (a few
+    sinusoids, up to about 1.5 rad/s) is integrated the way va2rot does; the ground-truth rotations are that chain times a small
+    random rotation (up to 0.3 rad) and the ground-truth velocities the smooth ones plus noise, so predicted and true rotations
+    stay within about 1 rad of each other.  The features are a fixed random projection of (angular velocity, step length) plus
+    noise: there is something to learn.  Feature rows past seq_len are zero; poses and velocities are given for every frame.
+    'gravitynet' (HN:118-155, 334-342): head_rot_mat [B, window + 1, 3, 3], head_trans [B, window + 1, 3] (from the origin), both
+    in a frame tilted against gravity by up to 0.5 rad, floor_normal [B, 3, 1] (the unit normal in that frame), seq_len [B] =
+    window + 1 (`lengths` is not supported: the reference pads GravityNet's input for single sequences only)."""
+    if kind not in ("headnet", "gravitynet"):
+        raise ValueError(f"unknown stage-1 kind {kind!r}")
+    r = _rng(seed, f"stage1_train_batch.{kind}")
+    T = window
+    t = np.arange(T + 1)[None, :, None] / 30.0
+    amp, freq, ph = r.uniform(0.1, 0.5, (B, 1, 3, 3)), r.uniform(0.3, 2.0, (B, 1, 3, 3)), r.uniform(0, 2 * np.pi, (B, 1, 3, 3))
+    va = (amp * np.sin(2 * np.pi * freq * t[..., None] + ph)).sum(-1)  # [B, T + 1, 3], body frame
+    q = r.standard_normal((B, 4))
+    q[:, 0] = np.abs(q[:, 0]) + 1.0
+    q /= np.linalg.norm(q, axis=-1, keepdims=True)
+    chain = [q]
+    for i in range(T):
+        zero = np.zeros((B, 1))
+        conj = q * np.array([1.0, -1.0, -1.0, -1.0])
+        angv = _np_qmul(_np_qmul(q, np.concatenate((zero, va[:, i]), -1)), conj)[:, 1:]
+        n = _np_qmul(_np_aa2q(angv / 30.0), q)
+        n = np.where(n[:, :1] < 0, -n, n)
+        q = n / np.linalg.norm(n, axis=-1, keepdims=True)
+        chain.append(q)
+    chain = np.stack(chain, 1)  # [B, T + 1, 4]
+    speed = r.uniform(0.2, 1.5, (B, 1, 1)) * (1 + 0.5 * np.sin(2 * np.pi * r.uniform(0.2, 1.0, (B, 1, 1)) * t + r.uniform(0, 6, (B, 1, 1))))
+    heading = r.uniform(0, 2 * np.pi, (B, 1, 1)) + r.uniform(-1, 1, (B, 1, 1)) * t
+    vel = np.concatenate((speed * np.cos(heading), speed * np.sin(heading), 0.05 * np.sin(3 * t + r.uniform(0, 6, (B, 1, 1)))), -1)
+    trans = np.concatenate((np.zeros((B, 1, 3)), np.cumsum(vel[:, :-1], 1) / 30.0), 1)
+    trans[..., 2] += 1.6
+    if kind == "headnet":
+        axis = r.standard_normal((B, T + 1, 3))
+        axis /= np.linalg.norm(axis, axis=-1, keepdims=True)
+        gt_q = _np_qmul(chain, _np_aa2q(axis * r.uniform(0.0, 0.3, (B, T + 1, 1))))
+        gt_q[:, 0] = chain[:, 0]
+        gt_q /= np.linalg.norm(gt_q, axis=-1, keepdims=True)
+        head_vels = np.concatenate((vel[:, :T], va[:, :T] + 0.05 * r.standard_normal((B, T, 3))), -1)
+        step = np.linalg.norm(trans[:, 1:] - trans[:, :-1], axis=-1, keepdims=True)
+        proj = _rng(0, "stage1_train_batch.projection").standard_normal((4, 512)) * 0.5
+        of = np.concatenate((va[:, :T], 30.0 * step), -1) @ proj + 0.3 * r.standard_normal((B, T, 512))
+        seq_len = np.full(B, T) if lengths is None else np.asarray(lengths).reshape(B)
+        if seq_len.min() < 0 or seq_len.max() > T:
+            raise ValueError(f"lengths span {seq_len.min()}..{seq_len.max()}: 0..{T} expected")
+        of = of * (np.arange(T)[None, :, None] < seq_len[:, None, None])  # feature rows past a sequence's end are zero padding
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+        return {"of": f32(of), "head_pose": f32(np.concatenate((trans, gt_q), -1)), "head_vels": f32(head_vels),
+                "seq_len": torch.from_numpy(seq_len.astype(np.int64))}
+    if lengths is not None:
+        raise ValueError("lengths: GravityNet's training batches have window + 1 frames each")
+    axis = r.standard_normal((B, 3))
+    axis[:, 2] = 0.0
+    axis /= np.linalg.norm(axis, axis=-1, keepdims=True)
+    G = _np_q2mat(_np_aa2q(axis * r.uniform(0.05, 0.5, (B, 1))))  # the tilt of the SLAM frame against gravity
+    rot = np.einsum("bij,btjk->btik", G, _np_q2mat(chain))
+    tr0 = trans - trans[:, :1]
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    return {"head_rot_mat": f32(rot), "head_trans": f32(np.einsum("bij,btj->bti", G, tr0)),
+            "floor_normal": f32(G[:, :, 2])[:, :, None], "seq_len": torch.full((B,), T + 1, dtype=torch.int64)}
+
+
 # ------------------------------------------------------------------------------------------ stage 1's optical-flow CNN (ResNet-18)
 FLOW_IMG = 224
 FLOW_FEATS = 512

@@ -163,3 +163,96 @@ class Stage2Trainer:
                 padding_mask = self.prep_padding_mask(val_data, val["seq_len"])
                 self.last_sample = self.ema.ema_model.sample(val_data, cond_mask, padding_mask=padding_mask)
         self.save(milestone)
+
+
+class Stage1Trainer:
+    """The reference's two stage-1 loops (trainer_head_estimation.py:78-212 for HeadFormer, trainer_amass_head_gravity_normal_
+    estimation.py:60-173 for HeadNormalFormer) over any iterable of reference-format batch dicts, without wandb and plots:
+    per iteration forward, compute_loss, zero_grad, backward, clip_grad_norm_(1.0, error_if_nonfinite=False), AdamW step; StepLR
+    (gamma 0.3; step_size 1000 for HeadNet and 2000 for GravityNet unless given) stepped per epoch; the validation loss in eval()
+    mode under no_grad at the first iteration of every epoch with (epoch + 1) % validation_iter == 0 (at most val_batches_max
+    batches; the HeadNet loop's 50); a checkpoint train-<epoch>.pt every save_interval epochs with the reference's keys {'epoch',
+    'transformer_encoder_state_dict', 'optimizer_state_dict', 'loss'}.
+
+    The model is a stage1.HeadFormer or stage1.HeadNormalFormer with its parameters on the GPU; the trainer sets hip_training (the
+    gradients come from egoego_s1_train_backward) and train() mode.  The update is torch.optim.AdamW: optim.FusedAdam has neither
+    decoupled weight decay nor clipping.  Nothing is read back from the device inside an epoch; `history` holds one dict of epoch
+    means (device work done once per epoch), `val_history` the validation means."""
+
+    def __init__(self, model, train_batches, val_batches=None, *, lr=1e-4, step_size=None, gamma=0.3, validation_iter=1,
+                 save_interval=50, save_dir="./results", val_batches_max=50, max_grad_norm=1.0):
+        self.model = model
+        self.train_batches, self.val_batches = train_batches, val_batches
+        self.headnet = model.cfg.kind == "headnet"
+        self.keys = ("loss", "orient", "va", "dist") if self.headnet else ("loss", "normal")
+        model.hip_training = True
+        model.train()
+        self.optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
+        if step_size is None:
+            step_size = 1000 if self.headnet else 2000
+        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=step_size, gamma=gamma)
+        self.validation_iter, self.save_interval = int(validation_iter), int(save_interval)
+        self.save_dir, self.val_batches_max, self.max_grad_norm = save_dir, int(val_batches_max), float(max_grad_norm)
+        self.epoch = 0
+        self.history, self.val_history = [], []
+        self.last_loss = None
+
+    def _path(self, epoch):
+        return os.path.join(self.save_dir, "weights", f"train-{epoch}.pt")
+
+    def save(self, epoch):
+        os.makedirs(os.path.dirname(self._path(epoch)), exist_ok=True)
+        torch.save({"epoch": epoch, "transformer_encoder_state_dict": self.model.state_dict(),
+                    "optimizer_state_dict": self.optimizer.state_dict(), "loss": self.last_loss}, self._path(epoch))
+        return self._path(epoch)
+
+    def load(self, path):
+        ck = torch.load(path, map_location=next(self.model.parameters()).device)
+        self.model.load_state_dict(ck["transformer_encoder_state_dict"])
+        self.optimizer.load_state_dict(ck["optimizer_state_dict"])
+        self.epoch = int(ck["epoch"])
+        self.last_loss = ck.get("loss")
+
+    def step(self, batch):
+        """One iteration -> the loss parts (detached device scalars, in the order of self.keys)."""
+        out = self.model(batch)
+        parts = self.model.compute_loss(out, batch)
+        self.optimizer.zero_grad()
+        parts[0].backward()
+        torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm, error_if_nonfinite=False)
+        self.optimizer.step()
+        self.last_loss = parts[0].detach()
+        return tuple(p.detach() for p in parts)
+
+    def validate(self):
+        """The mean loss parts over (at most val_batches_max of) the validation batches, in eval() mode under no_grad."""
+        was_training = self.model.training
+        self.model.eval()
+        got = []
+        with torch.no_grad():
+            for i, batch in enumerate(self.val_batches):
+                if i >= self.val_batches_max:
+                    break
+                got.append(torch.stack([p.detach().double() for p in self.model.compute_loss(self.model(batch), batch)]))
+        self.model.train(was_training)
+        if not got:
+            return None
+        return dict(zip(self.keys, torch.stack(got).mean(0).tolist()))
+
+    def train(self, epochs):
+        """Runs `epochs` more epochs -> self.epoch."""
+        for _ in range(epochs):
+            self.epoch += 1
+            got = []
+            for it, batch in enumerate(self.train_batches):
+                got.append(torch.stack([p.double() for p in self.step(batch)]))
+                if self.val_batches is not None and (self.epoch + 1) % self.validation_iter == 0 and it == 0:
+                    v = self.validate()
+                    if v is not None:
+                        self.val_history.append(dict(v, epoch=self.epoch))
+            if got:
+                self.history.append(dict(zip(self.keys, torch.stack(got).mean(0).tolist()), epoch=self.epoch))
+            self.scheduler.step()
+            if self.epoch % self.save_interval == 0:
+                self.save(self.epoch)
+        return self.epoch

@@ -771,6 +771,77 @@ int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, co
  * a synchronisation, to read counters for tests and logging. */
 int egoego_optim_read_state(egoego_optim_ctx* ctx, const void* d_state, size_t state_bytes, egoego_optim_state* d_out, void* stream);
 
+/* ==================================================================================================================
+ * Stage-1 training (egoego_s1_train_*, egoego_s1_headnet_loss; added under ABI 8, purely additive): the training encode of
+ * HeadNet and GravityNet (the TM Decoder at d_model 256 plus the ReLU MLP heads) with the gradient of every trainable tensor, and
+ * HeadNet's loss (HE:97-119, 310-345) with its gradient with respect to the heads.  The conventions of egoego_train_* hold: the
+ * weights are the caller's LIVE fp32 tensors (egoego_s1_weights, read in place, never packed); a call only enqueues work on
+ * `stream` (no allocation, no host copy, no synchronisation); `saves` (256-byte aligned, egoego_s1_train_saves_bytes) is filled by
+ * the forward call and read by the backward call, one per outstanding graph; the workspace is scratch of one call and neither
+ * buffer's content on entry matters; every sum over rows runs over fixed chunks whose partials are added in order in fp64, without
+ * float atomics; dropout (three sites per layer) is Philox keyed by (seed; layer, site, window id, element within the window).
+ * Contractions are split-bf16 (three bf16 MFMAs, fp32 accumulate); LayerNorm, softmax and residuals fp32; the loss fp64.
+ * egoego_s1_train_last_error() describes the last failure of any call of this section.
+ * ================================================================================================================== */
+typedef struct egoego_s1_train_ctx egoego_s1_train_ctx;
+/* egoego_s1_train_saved: the EGOEGO_TRAIN_SAVED_* tensors of a decoder layer ([W][window][256], ATTN_PROB [W][4][window][window],
+ * ATTN_OUT [W][window][1024]) and the heads' hidden rows (after the ReLU; `layer` then counts the heads' Linears as head_w does). */
+enum { EGOEGO_S1_TRAIN_SAVED_HEAD_HIDDEN = 6 };
+
+/* Caller-allocated fp32 device buffers, one per trainable tensor, in the layout of egoego_s1_weights.  position_vec is frozen:
+ * its slot is not read. */
+typedef struct {
+    float* start_conv_w; float* start_conv_b;
+    float* position_vec;  /* unused */
+    const egoego_train_layer_grads* layers;  /* HOST array of n_dec_layers entries */
+    float* head_w[8];
+    float* head_b[8];
+} egoego_s1_train_grads;
+
+const char* egoego_s1_train_last_error(void);
+/* cfg as for egoego_s1_ctx_create: d_model 256, 4 x 256 heads, window 1..128, 1..8 layers, either kind. */
+int egoego_s1_train_ctx_create(const egoego_s1_config* cfg, int device, egoego_s1_train_ctx** out);
+void egoego_s1_train_ctx_destroy(egoego_s1_train_ctx* ctx);
+/* 0 (egoego_s1_train_last_error() says why) for a shape no call accepts. */
+size_t egoego_s1_train_workspace_bytes(const egoego_s1_train_ctx* ctx, int n_windows);
+size_t egoego_s1_train_saves_bytes(const egoego_s1_train_ctx* ctx, int n_windows);
+/* d_feats [W][window][d_feats] fp32 and d_valid int32 [W] as for egoego_s1_encode (rows past valid[w] are read as zero rows,
+ * whatever they hold) -> d_heads [W][window][4] (va | dist, HeadNet) or [W][3] (GravityNet, from token 0 of each window).
+ * d_window_ids int64 [W] or NULL (window w has id w): the dropout streams; p_drop = 0: no dropout. */
+int egoego_s1_train_forward(egoego_s1_train_ctx* ctx, const egoego_s1_weights* w, const float* d_feats, const int32_t* d_valid,
+                            float p_drop, uint64_t dropout_seed, const int64_t* d_window_ids, int n_windows, void* d_saves,
+                            size_t saves_bytes, void* d_workspace, size_t workspace_bytes, float* d_heads, void* stream);
+/* From the saves of the forward call with the same weights, p_drop, dropout_seed and n_windows, and any upstream gradient
+ * d_dheads of d_heads' shape: the gradient of every buffer of `grads` (overwritten). */
+int egoego_s1_train_backward(egoego_s1_train_ctx* ctx, const egoego_s1_weights* w, const void* d_saves, size_t saves_bytes,
+                             const float* d_dheads, const egoego_s1_train_grads* grads, float p_drop, uint64_t dropout_seed,
+                             int n_windows, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The mask (1 keep / 0 drop, one byte each) a forward call with these arguments applies at `site` (EGOEGO_TRAIN_SITE_*) of `layer`:
+ * site 0 [W][4][window][window], sites 1 and 2 [W][window][256].  The workspace holds the implied ids when d_window_ids is NULL. */
+int egoego_s1_train_dropout_mask(egoego_s1_train_ctx* ctx, float p_drop, uint64_t dropout_seed, int layer, int site,
+                                 const int64_t* d_window_ids, int n_windows, uint8_t* d_out, void* d_workspace, size_t workspace_bytes,
+                                 void* stream);
+/* Test/debug: copies saved tensor `which` of `layer` out of the saves of a forward call. */
+int egoego_s1_train_saved(egoego_s1_train_ctx* ctx, const void* d_saves, size_t saves_bytes, int n_windows, int layer, int which,
+                          float* d_out, void* stream);
+
+/* HeadNet's loss and its gradient with respect to the heads, fp64 on fp32 inputs, no context: d_heads [B][window][4] (va | dist)
+ * of which the first T <= window <= 128 rows of each sequence count; d_head_pose [B][T + 1][7] (xyz, quaternion w,x,y,z);
+ * d_head_vels [B][T][6] (its last three columns are the angular velocity).  With q_0 = head_pose[b][0][3:] and
+ * q_{t+1} = normalize(standardize(axis_angle_to_quaternion(quaternion_apply(q_t, va_t) / 30) (x) q_t)) (pytorch3d's formulas; q_t is
+ * a constant of step t, as va2rot detaches it):
+ *   orient = mean sum((|standardize(gt_{t+1} (x) conj(q_{t+1}))| - [1,0,0,0])^2),  va = mean |head_vels[..., 3:] - va|^2,
+ *   dist = mean (dist - dist_scale |trans_{t+1} - trans_t|)^2, every mean over all B * T frames;
+ *   d_loss[4] = (w_rotation orient + w_va va + w_dist dist, orient, va, dist)
+ *   d_dheads64 / d_dheads (fp64 / fp32, either may be NULL) [B][window][4] = d(total) / d(heads), rows t >= T zero.
+ * One workgroup per sequence walks the chain once; frame t's term and its gradient with respect to va_t come from one forward-mode
+ * evaluation.  Sums: a fixed tree over a sequence's frames, then the sequences in order.  The workspace
+ * (egoego_s1_headnet_loss_workspace_bytes, 256-byte aligned) may hold anything on entry. */
+size_t egoego_s1_headnet_loss_workspace_bytes(int B);
+int egoego_s1_headnet_loss(const float* d_heads, int window, int B, int T, const float* d_head_pose, const float* d_head_vels,
+                           double dist_scale, double w_rotation, double w_va, double w_dist, double* d_loss, double* d_dheads64,
+                           float* d_dheads, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""Train a stage-1 estimator on the HIP path: the reference's trainer_head_estimation.py (HeadNet) or trainer_amass_head_gravity_
+normal_estimation.py (GravityNet) loop through egoego_release_amd.trainer.Stage1Trainer, without wandb and plots.
+
+    python tools/train_stage1.py --kind headnet --epochs 20 --save_dir runs/headnet             seeded synthetic batches
+    python tools/train_stage1.py --kind gravitynet --batches train.pt --val_batches val.pt ...  torch.save'd lists of batch dicts
+
+A batch dict is what the reference's DataLoader yields (synthetic.make_stage1_train_batch documents the keys); the stage-1 datasets
+themselves are not part of this package.  Checkpoints <save_dir>/weights/train-<epoch>.pt hold the reference's keys ('epoch',
+'transformer_encoder_state_dict', 'optimizer_state_dict', 'loss'): HeadFormer.load_state_dict and tools/run_egoego_demo.py take them.
+A GPU is required: there is no CPU path.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from egoego_release_amd import stage1  # noqa: E402
+from egoego_release_amd.synthetic import make_stage1_train_batch  # noqa: E402
+from egoego_release_amd.trainer import Stage1Trainer  # noqa: E402
+
+
+def parse_opt(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--kind", choices=("headnet", "gravitynet"), default="headnet")
+    p.add_argument("--save_dir", default="runs/stage1")
+    p.add_argument("--batches", default=None, help="a torch.save'd list of training batch dicts (default: seeded synthetic batches)")
+    p.add_argument("--val_batches", default=None)
+    p.add_argument("--synthetic_batches", type=int, default=8, help="synthetic batches per epoch when --batches is not given")
+    p.add_argument("--batch_size", type=int, default=32)
+    p.add_argument("--epochs", type=int, default=1000)
+    p.add_argument("--save_interval", type=int, default=50)
+    p.add_argument("--validation_iter", type=int, default=1)
+    p.add_argument("--learning_rate", type=float, default=1e-4)
+    p.add_argument("--window", type=int, default=None, help="default: 90 (HeadNet) / 120 (GravityNet)")
+    p.add_argument("--n_dec_layers", type=int, default=2)
+    p.add_argument("--n_head", type=int, default=4)
+    p.add_argument("--d_k", type=int, default=256)
+    p.add_argument("--d_v", type=int, default=256)
+    p.add_argument("--d_model", type=int, default=256)
+    p.add_argument("--w_rotation", type=float, default=1.0)
+    p.add_argument("--w_va", type=float, default=1.0)
+    p.add_argument("--w_dist", type=float, default=1.0)
+    p.add_argument("--dist_scale", type=float, default=10.0)
+    p.add_argument("--resume", default=None, help="a checkpoint to continue from")
+    p.add_argument("--device", default="cuda")
+    opt = p.parse_args(argv)
+    if opt.window is None:
+        opt.window = 90 if opt.kind == "headnet" else 120
+    opt.input_of_feats = True
+    return opt
+
+
+def main(argv=None):
+    opt = parse_opt(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("train_stage1 needs a ROCm GPU: there is no CPU path")
+    dev = torch.device(opt.device)
+    cls = stage1.HeadFormer if opt.kind == "headnet" else stage1.HeadNormalFormer
+    model = cls(opt, dev).to(dev)
+    load = lambda path: torch.load(path, map_location="cpu")  # noqa: E731
+    if opt.batches:
+        train, val = load(opt.batches), (load(opt.val_batches) if opt.val_batches else None)
+    else:
+        train = [make_stage1_train_batch(opt.kind, opt.batch_size, opt.window, seed=s) for s in range(opt.synthetic_batches)]
+        val = [make_stage1_train_batch(opt.kind, opt.batch_size, opt.window, seed=10_000 + s) for s in range(2)]
+    tr = Stage1Trainer(model, train, val, lr=opt.learning_rate, validation_iter=opt.validation_iter, save_interval=opt.save_interval,
+                       save_dir=opt.save_dir)
+    if opt.resume:
+        tr.load(opt.resume)
+    os.makedirs(opt.save_dir, exist_ok=True)
+    with open(os.path.join(opt.save_dir, "opt.json"), "w") as f:
+        json.dump(vars(opt), f, indent=1, sort_keys=True)
+    for _ in range(opt.epochs):
+        tr.train(1)
+        line = {"epoch": tr.epoch, "train": tr.history[-1] if tr.history else None}
+        if tr.val_history and tr.val_history[-1]["epoch"] == tr.epoch:
+            line["val"] = tr.val_history[-1]
+        print(json.dumps(line), flush=True)
+    if tr.epoch % opt.save_interval != 0:
+        tr.save(tr.epoch)
+    print(json.dumps({"checkpoint": tr._path(tr.epoch)}))
+
+
+if __name__ == "__main__":
+    main()
