@@ -115,7 +115,8 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_optim_state_bytes", "egoego_optim_set_tensors", "egoego_optim_step", "egoego_optim_read_state",
            "egoego_s1_train_last_error", "egoego_s1_train_ctx_create", "egoego_s1_train_ctx_destroy", "egoego_s1_train_workspace_bytes",
            "egoego_s1_train_saves_bytes", "egoego_s1_train_forward", "egoego_s1_train_backward", "egoego_s1_train_dropout_mask",
-           "egoego_s1_train_saved", "egoego_s1_headnet_loss_workspace_bytes", "egoego_s1_headnet_loss"]
+           "egoego_s1_train_saved", "egoego_s1_headnet_loss_workspace_bytes", "egoego_s1_headnet_loss",
+           "egoego_s1_data_last_error", "egoego_s1_gravity_batch"]
 S1_TRAIN_SAVED = {"ffn_hidden": 0, "attn_prob": 1, "attn_out": 2, "attn_ln": 3, "layer_out": 4, "layer_in": 5, "head_hidden": 6}
 LOSS_L1, LOSS_L2 = 0, 1
 TRAIN_SITE_ATTN, TRAIN_SITE_FC, TRAIN_SITE_FFN = 0, 1, 2
@@ -289,6 +290,10 @@ def load():
     lib.egoego_s1_headnet_loss_workspace_bytes.restype = sz
     # heads, window, B, T, head_pose, head_vels, dist_scale, w_rotation, w_va, w_dist, loss, d_heads fp64, d_heads fp32, workspace, bytes, stream
     lib.egoego_s1_headnet_loss.argtypes = [vp, i32, i32, i32, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, sz, vp]
+    lib.egoego_s1_data_last_error.restype = C.c_char_p
+    # pose, rows, offsets, sequences, seq ids, draw ids, B, window, seed, for_eval, planted start / rot / scale, ori_head_pose,
+    # head_rot_mat, head_trans, seq_len, aligned_rot_mat, aligned_scale, floor_normal, start_t_idx, aug_scale, stream
+    lib.egoego_s1_gravity_batch.argtypes = [vp, i32, vp, i32, vp, vp, i32, i32, u64, i32, vp, vp, vp] + [vp] * 9 + [vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -319,3 +324,4 @@ check_amass = _checker("AMASS-preprocessing ", "egoego_amass_last_error")
 check_train = _checker("training-step ", "egoego_train_last_error")
 check_optim = _checker("parameter-update ", "egoego_optim_last_error")
 check_s1_train = _checker("stage-1 training ", "egoego_s1_train_last_error")
+check_s1_data = _checker("stage-1 data ", "egoego_s1_data_last_error")

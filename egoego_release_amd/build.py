@@ -9,7 +9,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libegoego_hip.so")
 PERFDEBUG_DIR = os.path.join(os.path.dirname(PKG), "tools", "_build")
 SOURCES = ["egoego_hip.hip", "stage1.hip", "flow_cnn.hip", "body_model.hip", "eval_metrics.hip", "motion_windows.hip", "amass_prep.hip", "train_step.hip",
-           "optim_step.hip", "stage1_train.hip"]
+           "optim_step.hip", "stage1_train.hip", "stage1_data.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "egoego_hip.h")]
 
 

@@ -647,10 +647,17 @@ class HeadNormalFormer(_Stage1Module):
 
     def forward(self, data):
         """HN:118-155: the floor normal of every sequence from its first window + 1 frames.  With hip_training set and grad mode
-        on, pred_normal is connected to the parameters (the training encode)."""
+        on, pred_normal is connected to the parameters (the training encode).  data['lengths'] (int32 [B] on the device; the
+        batches of stage1_data carry it, no reference-format dict does): the frames of each padded sequence, so that the keys are
+        masked by seq_len - 1 as in HN:148; without the key every sequence counts with all its rows."""
         eng = self._exec_engine()
         rot, trans, ln = self._frames(data)
         B, L = rot.shape[:2]
+        if "lengths" in data:
+            ln = data["lengths"]
+            if not isinstance(ln, torch.Tensor) or ln.device != eng.device or ln.dtype != torch.int32 or tuple(ln.shape) != (B,):
+                raise ValueError(f"lengths: an int32 [{B}] tensor on {eng.device} expected")
+            ln = ln.clamp(max=L).contiguous()  # (the feature kernel reads rows below a sequence's length: never past the L it was given)
         win = self.cfg.window
         feats = torch.empty(B, win, 18, device=eng.device)
         valid = torch.empty(B, dtype=torch.int32, device=eng.device)

@@ -172,7 +172,9 @@ class Stage1Trainer:
     (gamma 0.3; step_size 1000 for HeadNet and 2000 for GravityNet unless given) stepped per epoch; the validation loss in eval()
     mode under no_grad at the first iteration of every epoch with (epoch + 1) % validation_iter == 0 (at most val_batches_max
     batches; the HeadNet loop's 50); a checkpoint train-<epoch>.pt every save_interval epochs with the reference's keys {'epoch',
-    'transformer_encoder_state_dict', 'optimizer_state_dict', 'loss'}.
+    'transformer_encoder_state_dict', 'optimizer_state_dict', 'loss'}, plus 'data_state' when train_batches has a state_dict() (a
+    stage1_data.GravityBatches: its epoch count and shuffle generator, so that a resumed run draws the batches the uninterrupted
+    run would have).
 
     The model is a stage1.HeadFormer or stage1.HeadNormalFormer with its parameters on the GPU; the trainer sets hip_training (the
     gradients come from egoego_s1_train_backward) and train() mode.  The update is torch.optim.AdamW: optim.FusedAdam has neither
@@ -202,8 +204,11 @@ class Stage1Trainer:
 
     def save(self, epoch):
         os.makedirs(os.path.dirname(self._path(epoch)), exist_ok=True)
-        torch.save({"epoch": epoch, "transformer_encoder_state_dict": self.model.state_dict(),
-                    "optimizer_state_dict": self.optimizer.state_dict(), "loss": self.last_loss}, self._path(epoch))
+        data = {"epoch": epoch, "transformer_encoder_state_dict": self.model.state_dict(),
+                "optimizer_state_dict": self.optimizer.state_dict(), "loss": self.last_loss}
+        if hasattr(self.train_batches, "state_dict"):  # a batch source with epochs of its own (stage1_data.GravityBatches)
+            data["data_state"] = self.train_batches.state_dict()
+        torch.save(data, self._path(epoch))
         return self._path(epoch)
 
     def load(self, path):
@@ -212,6 +217,8 @@ class Stage1Trainer:
         self.optimizer.load_state_dict(ck["optimizer_state_dict"])
         self.epoch = int(ck["epoch"])
         self.last_loss = ck.get("loss")
+        if "data_state" in ck and hasattr(self.train_batches, "load_state_dict"):
+            self.train_batches.load_state_dict(ck["data_state"])
 
     def step(self, batch):
         """One iteration -> the loss parts (detached device scalars, in the order of self.keys)."""

@@ -842,6 +842,34 @@ int egoego_s1_headnet_loss(const float* d_heads, int window, int B, int T, const
                            double dist_scale, double w_rotation, double w_va, double w_dist, double* d_loss, double* d_dheads64,
                            float* d_dheads, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ==================================================================================================================
+ * GravityNet's training batches (egoego_s1_gravity_batch; added under ABI 8, purely additive): AMASSHeadPoseDataset.__getitem__
+ * with augment_traj (amass_headpose_dataset.py:38-76, 115-165) for the B samples of a batch in ONE launch on `stream`: no
+ * allocation, no host copy, no synchronisation, no workspace; every output is the caller's and is written whole.
+ *   d_pose [n_rows][7] fp32 (xyz, quaternion w,x,y,z): the head poses of a split's n_seqs sequences, packed; d_offsets int32
+ *   [n_seqs + 1]: sequence k is rows offsets[k] .. offsets[k + 1] - 1; d_seq_ids int32 [B]: the sequence of each sample;
+ *   d_draw_ids int64 [B]: a sample's draws are a function of (seed, draw id) alone.
+ * With len the sequence's rows and W = window: len - W - 1 <= 0 -> start 0, n = len frames; else n = W + 1 and start = 0 under
+ * for_eval, else (word * (len - W - 1)) >> 32.  Rr = quaternion_to_matrix(o / copysign(|o|, o_0)) of four normals o, rounded to
+ * fp32; s = 0.1 + 9.9 (word + 0.5) 2^-32 formed in fp64 and rounded to fp32.  The draws are Philox4x32-10 keyed by `seed` at the
+ * counters (draw id low, draw id high, 0: the normals | 1: word 0 the start, word 1 the scale, 0x47424154); dropout and the sampler's
+ * noise keep word 3 below 1000, so no counter of theirs coincides.  d_start int32 [B], d_rot fp32 [B][9], d_scale fp32 [B]: planted
+ * draws, each NULL for "draw it".  Arithmetic fp64 on the fp32 inputs, each output rounded once:
+ *   d_ori_head_pose [B][W + 1][7] the window's rows as they are; d_head_rot_mat [B][W + 1][3][3] = Rr R(q_t) (two_s = 2 / |q|^2);
+ *   d_head_trans [B][W + 1][3] = s Rr (p_t - p_0) (the reference's serial sum of scaled differences, telescoped); rows n .. W of
+ *   these three are zero; d_seq_len int32 [B] = n; d_aligned_rot_mat [B][3][3] = Rr^T; d_aligned_scale [B] = 1 / s (divided in
+ *   fp64); d_floor_normal [B][3] = Rr[:, 2]; d_start_t_idx int32 [B] and d_aug_scale [B]: the start and s used.
+ * A sample whose sequence id, offsets or planted start do not describe rows inside d_pose is written as an empty sample (n = 0,
+ * all rows zero); nothing outside the arrays is read.  EGOEGO_E_INVALID before any launch: window < 1, B < 1, n_rows < 1,
+ * n_seqs < 1, a NULL pointer other than the three planted draws.  egoego_s1_data_last_error() describes the last failure.
+ * ================================================================================================================== */
+const char* egoego_s1_data_last_error(void);
+int egoego_s1_gravity_batch(const float* d_pose, int n_rows, const int32_t* d_offsets, int n_seqs, const int32_t* d_seq_ids,
+                            const int64_t* d_draw_ids, int B, int window, uint64_t seed, int for_eval, const int32_t* d_start,
+                            const float* d_rot, const float* d_scale, float* d_ori_head_pose, float* d_head_rot_mat, float* d_head_trans,
+                            int32_t* d_seq_len, float* d_aligned_rot_mat, float* d_aligned_scale, float* d_floor_normal,
+                            int32_t* d_start_t_idx, float* d_aug_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

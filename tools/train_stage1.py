@@ -4,15 +4,20 @@ normal_estimation.py (GravityNet) loop through egoego_release_amd.trainer.Stage1
 
     python tools/train_stage1.py --kind headnet --epochs 20 --save_dir runs/headnet             seeded synthetic batches
     python tools/train_stage1.py --kind gravitynet --batches train.pt --val_batches val.pt ...  torch.save'd lists of batch dicts
+    python tools/train_stage1.py --kind gravitynet --motion train_amass_smplh_motion.p [--val_motion test_amass_smplh_motion.p] ...
+                                                      GravityNet on the head poses of a motion file (tools/process_amass.py)
 
-A batch dict is what the reference's DataLoader yields (synthetic.make_stage1_train_batch documents the keys); the stage-1 datasets
-themselves are not part of this package.  Checkpoints <save_dir>/weights/train-<epoch>.pt hold the reference's keys ('epoch',
+A batch dict is what the reference's DataLoader yields (synthetic.make_stage1_train_batch documents the keys).  --motion builds
+GravityNet's batches on the GPU (egoego_release_amd.stage1_data.GravityBatches: random windows, one random rotation and scale per
+sample) from the file's `head_qpos`; without --val_motion the file is split by dataset name as the reference's divide_train_val
+does.  HeadNet's datasets (they need optical-flow features) are not part of this package.  Checkpoints <save_dir>/weights/train-<epoch>.pt hold the reference's keys ('epoch',
 'transformer_encoder_state_dict', 'optimizer_state_dict', 'loss'): HeadFormer.load_state_dict and tools/run_egoego_demo.py take them.
 A GPU is required: there is no CPU path.
 """
 import argparse
 import json
 import os
+import pickle
 import sys
 
 import torch
@@ -29,6 +34,9 @@ def parse_opt(argv=None):
     p.add_argument("--save_dir", default="runs/stage1")
     p.add_argument("--batches", default=None, help="a torch.save'd list of training batch dicts (default: seeded synthetic batches)")
     p.add_argument("--val_batches", default=None)
+    p.add_argument("--motion", default=None, help="gravitynet: a motion file (joblib / pickle) whose entries hold head_qpos [T, 7]")
+    p.add_argument("--val_motion", default=None, help="a second motion file for validation (default: --motion split by dataset name)")
+    p.add_argument("--data_seed", type=int, default=0, help="--motion: the seed of the shuffle and of the augmentation draws")
     p.add_argument("--synthetic_batches", type=int, default=8, help="synthetic batches per epoch when --batches is not given")
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--epochs", type=int, default=1000)
@@ -51,7 +59,35 @@ def parse_opt(argv=None):
     if opt.window is None:
         opt.window = 90 if opt.kind == "headnet" else 120
     opt.input_of_feats = True
+    if opt.motion and opt.kind != "gravitynet":
+        p.error("--motion feeds GravityNet only (HeadNet's data needs optical-flow features)")
+    if opt.val_motion and not opt.motion:
+        p.error("--val_motion needs --motion")
     return opt
+
+
+def load_any(path):
+    try:
+        import joblib
+        return joblib.load(path)
+    except Exception:
+        with open(path, "rb") as f:
+            return pickle.load(f)
+
+
+def motion_batches(opt, dev):
+    """-> (train, val) GravityBatches of --motion / --val_motion (val None when the split leaves no validation sequence)."""
+    from egoego_release_amd.stage1_data import GravityBatches, _head_poses, split_by_dataset
+    kw = dict(window=opt.window, seed=opt.data_seed, device=dev)
+    data = load_any(opt.motion)
+    if opt.val_motion:
+        return (GravityBatches(data, opt.batch_size, **kw),
+                GravityBatches(load_any(opt.val_motion), opt.batch_size, train=False, shuffle=False, **kw))
+    train_names, val_names = split_by_dataset([n for n, _ in _head_poses(data, None)])
+    if not train_names:
+        raise SystemExit(f"{opt.motion}: no sequence of a training dataset (stage1_data.TRAIN_DATASETS); give --val_motion to train on all of it")
+    train = GravityBatches(data, opt.batch_size, names=train_names, **kw)
+    return train, (GravityBatches(data, opt.batch_size, train=False, shuffle=False, names=val_names, **kw) if val_names else None)
 
 
 def main(argv=None):
@@ -62,7 +98,9 @@ def main(argv=None):
     cls = stage1.HeadFormer if opt.kind == "headnet" else stage1.HeadNormalFormer
     model = cls(opt, dev).to(dev)
     load = lambda path: torch.load(path, map_location="cpu")  # noqa: E731
-    if opt.batches:
+    if opt.motion:
+        train, val = motion_batches(opt, dev)
+    elif opt.batches:
         train, val = load(opt.batches), (load(opt.val_batches) if opt.val_batches else None)
     else:
         train = [make_stage1_train_batch(opt.kind, opt.batch_size, opt.window, seed=s) for s in range(opt.synthetic_batches)]
