@@ -16,7 +16,9 @@
 //
 // Epilogue (fp32): v = acc * scale[n] + shift[n] (BatchNorm with its running statistics, folded at load into a per-channel
 // scale = w / sqrt(var + 1e-5) and shift = b - mean * scale, computed in fp64 and rounded once; fc: scale 1, shift = bias),
-// then + residual, then ReLU.
+// then + residual, then ReLU.  ReLU and the max-pool carry a NaN on, as the reference's F.relu and max_pool2d do (fmaxf
+// returns its other operand): a non-finite flow pixel ends as non-finite features of its frame, not as plausible numbers.
+// max_nan below is IEEE 754-2019 maximum, one v_maximum3_f32 on gfx950: fmaxf's bits for numbers (+0 above -0), NaN for a NaN.
 //
 // Bit-identity: an output element is one accumulator lane of one wave; its K loop runs in the same order whatever tile, chunk or
 // position its row falls in, and the rows of an MFMA do not interact.  A frame's features therefore do not depend on the others.
@@ -32,6 +34,8 @@
 #endif
 
 namespace fcnn {
+
+EG_D float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 
 static constexpr int BM = 128;   // rows (output pixels) per workgroup
 static constexpr int BK = 32;    // K per staged step
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(256) void flow_conv_kernel(ConvArgs a) {
                 const size_t o = (size_t)m * a.Cout + n;
                 float v = acc[tm][tn][r] * sc + sh;
                 if (a.res) v = v + a.res[o];
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = max_nan(v, 0.f);
                 a.y[o] = v;
             }
     }
@@ -235,7 +239,7 @@ __global__ void flow_maxpool_kernel(const float* x, float* y, int F, int H, int 
             const int iw = ow * 2 - 1 + kw;
             if (iw < 0 || iw >= W) continue;
             const float4 v = *(const float4*)(x + (((size_t)f * H + ih) * W + iw) * C + 4 * c4);
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+            m.x = max_nan(m.x, v.x); m.y = max_nan(m.y, v.y); m.z = max_nan(m.z, v.z); m.w = max_nan(m.w, v.w);
         }
     }
     *(float4*)(y + pix * C + 4 * c4) = m;

@@ -1,6 +1,21 @@
-"""The optical-flow ResNet-18 feature extractor on the MI355X: stage-wise parity with the fp64 oracle, bit-identity of a frame's
-features whatever the call around it, the drop-in layout and checkpoint path, the features through HIP HeadNet, and the
-extraction tool on an ARES demo layout."""
+"""The optical-flow ResNet-18 feature extractor on the MI355X.
+
+Parity, stage by stage: every (weight set, frame, stage) cell of tests/flow_cnn_cases.py is held to a bar derived from oracles,
+e_hip <= 2 (e_emul + e_32) + 2^-22 with e(a) = |a - r64|_2 / |r64|_2, for the whole stage; every live channel to the same on its
+own norms with the fp32-accumulation oracle's distance d_acc inside the sum (why: flow_cnn_cases.py); the other channels to the
+stage's bar on the stage's norm.  Stages 1-4 and the head are isolated: all three oracle modes take the HIP
+path's own previous-stage output (extract(..., stages=True), widened to fp64), so nothing accumulates across stages.  Weight
+sets: the seeded initialisation and two trained-like ones (folded scales over three decades, variances under eps, negative and
+zero BatchNorm weights, dead filters).  Frames: two flow fields, impulses at the corners, a constant, the all-zero flow, +-40 px
+and a 20x flow.  The older test against the chained fp64 oracle with one max-norm over all frames stays beside it.
+
+Also: bit-identity of a frame's features and stage tensors whatever the call and the chunk around it, re-packing after in-place
+parameter changes, a NaN or Inf pixel (it reaches every feature of its frame, as through the reference's ops, and no other
+frame), the drop-in layout and checkpoint path, the features through HIP HeadNet, and the extraction tool on an ARES demo layout.
+
+EGOEGO_FLOW_RECORD=<file>: the measured figures of every cell are written there as JSON (profiles/flow_cnn_stage_error.json is
+such a file)."""
+import json
 import os
 import subprocess
 import sys
@@ -10,6 +25,7 @@ import numpy as np
 import pytest
 import torch
 
+import flow_cnn_cases as K
 import flow_cnn_oracle as O
 import stage1_oracle as S1O
 from egoego_release_amd import stage1, synthetic
@@ -55,6 +71,114 @@ def test_stagewise_parity_with_fp64_oracle(model):
         assert e < STAGE_BAR, (i, e)
     assert ef < FEAT_BAR, ef
     assert torch.isfinite(feats).all()
+
+
+_RECORD = {}
+
+
+def _record(case, **kw):
+    path = os.environ.get("EGOEGO_FLOW_RECORD")
+    if not path:
+        return
+    _RECORD.setdefault(case, {}).update(kw)
+    with open(path, "w") as f:
+        json.dump(_RECORD, f, indent=1, sort_keys=True)
+
+
+def _module(wname):
+    return stage1.FlowFeatureExtractor(state_dict={k: v.clone() for k, v in K.weights(wname).items()}).to("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def case_frames():
+    return torch.from_numpy(K.frames())
+
+
+@pytest.fixture(scope="module")
+def init_call(case_frames):
+    """The init weights' module and its one 7-frame call with stages (shared: not modified)."""
+    m = _module("init")
+    feats, stages = m.extract(case_frames, stages=True)
+    return m, feats, stages
+
+
+@pytest.mark.parametrize("wname", K.WEIGHT_SETS)
+def test_every_stage_cell_meets_the_derived_bar(wname, case_frames, init_call):
+    """Measured on the MI355X (profiles/flow_cnn_stage_error.json), worst over the 126 cells, as fractions of the bar: whole stage
+    0.49 (e_hip / (e_emul + e_32) = 0.99), live channels 0.72, other channels 0.92.  Without d_acc the worst live channel is at 8.4
+    bars (features 7.0 to 8.4, layer4 up to 5.9, layer1-2 up to 1.4), with d_acc added once outside the factor at 1.03."""
+    if wname == "init":
+        _, feats, stages = init_call
+    else:
+        feats, stages = _module(wname).extract(case_frames, stages=True)
+    sd = K.weights(wname)
+    assert feats.shape == (7, 512) and [tuple(s.shape) for s in stages] == [(7,) + sh for sh in stage1.FlowCNNEngine.STAGE_SHAPES]
+    outs = [K.nchw64(s) for s in stages] + [feats.double().cpu()]
+    ins = [case_frames] + outs[:5]
+    bad, rec = [], {}
+    worst = {k: 0.0 for k in ("whole", "chan", "chan_plain", "chan_acc_once", "other", "ratio", "chan_ratio")}
+    for i, sname in enumerate(K.STAGE_NAMES):
+        r64, emul, f32, acc = (K.run(sd, i, ins[i], m) for m in ("f64", "emul", "f32", "acc"))
+        assert torch.isfinite(outs[i]).all(), sname
+        for n, fname in enumerate(K.FRAME_NAMES):
+            c = K.cell(outs[i][n], r64[n], emul[n], f32[n], acc[n])
+            rec[f"{sname}/{fname}"] = c
+            print("%-14s %-9s %-9s e_hip %.2e e_emul %.2e e_32 %.2e  over bar: whole %.3f channel %.3f (without d_acc %.3f, d_acc "
+                  "once %.3f) other %.3f  e/(e_emul+e_32): %.3f, worst channel %.3f  live %d" % (
+                      wname, sname, fname, c["e_hip"], c["e_emul"], c["e_32"], c["whole"], c["chan"], c["chan_plain"],
+                      c["chan_acc_once"], c["other"], c["ratio"], c["chan_ratio"], c["live"]))
+            for k in worst:
+                if np.isfinite(c[k]):
+                    worst[k] = max(worst[k], c[k])
+            if not K.passes(c):
+                bad.append((sname, fname, c))
+    print(wname, "worst:", {k: "%.3f" % v for k, v in worst.items()})
+    _record(wname, cells=rec, worst=worst)
+    assert not bad, bad
+
+
+def test_stage_tensors_are_bit_identical_alone_and_across_chunks(case_frames, init_call):
+    m, feats, stages = init_call
+    for n in (0, 2, 6):
+        f1, s1 = m.extract(case_frames[n:n + 1], stages=True)
+        assert torch.equal(f1, feats[n:n + 1]), n
+        for i in range(5):
+            assert torch.equal(s1[i], stages[i][n:n + 1]), (n, i)
+    small = stage1.FlowFeatureExtractor(state_dict=K.weights("init"), chunk_frames=3).to("cuda:0")  # chunks of 3, 3 and 1
+    assert small.engine().chunk_frames == 3
+    f3, s3 = small.extract(case_frames, stages=True)
+    assert torch.equal(f3, feats)
+    for i in range(5):
+        assert torch.equal(s3[i], stages[i]), i
+
+
+def test_statistics_and_weights_changed_in_place_are_repacked(case_frames):
+    m = _module("init")
+    fl = case_frames[:2]
+    before = m.extract(fl)
+    with torch.no_grad():
+        m.cnn.resnet.layer2[0].bn1.running_var.mul_(0.25)
+        m.cnn.resnet.layer1[1].conv2.weight.mul_(1.5)
+    feats, stages = m.extract(fl, stages=True)
+    assert not torch.equal(feats, before)
+    fresh = stage1.FlowFeatureExtractor(state_dict={k: v.detach().clone() for k, v in m.state_dict().items()}).to("cuda:0")
+    f2, s2 = fresh.extract(fl, stages=True)
+    assert torch.equal(feats, f2)
+    for i in range(5):
+        assert torch.equal(stages[i], s2[i]), i
+
+
+@pytest.mark.parametrize("value", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_a_non_finite_pixel_reaches_every_feature_of_its_frame_only(value, case_frames, init_call):
+    """As through the reference's ops (F.relu and max_pool2d propagate NaN; the CPU side is asserted in test_flow_cnn_cases.py)."""
+    m, feats, _ = init_call
+    fl = case_frames[:3].clone()
+    fl[1, 100, 57, 0] = value
+    out = m.extract(fl)
+    torch.cuda.synchronize()
+    assert torch.equal(out[0], feats[0]) and torch.equal(out[2], feats[2])
+    assert torch.equal(m.extract(case_frames[0:1])[0], out[0]) and torch.equal(m.extract(case_frames[2:3])[0], out[2])
+    assert not torch.isfinite(out[1]).any(), int(torch.isfinite(out[1]).sum())
 
 
 def test_frame_features_are_bit_identical_in_any_call(model):
