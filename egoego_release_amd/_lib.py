@@ -80,11 +80,16 @@ class OptimState(C.Structure):
     """egoego_optim_state: the head of the fused update's state block"""
     _fields_ = [("adam_step", C.c_int64), ("applied", C.c_int64), ("skipped", C.c_int64), ("total_norm", C.c_double),
                 ("total_norm_f32", C.c_float), ("last_skip", C.c_int32), ("step_size", C.c_float), ("bc2_sqrt", C.c_float),
-                ("one_minus_decay", C.c_float), ("ema_action", C.c_int32)]
+                ("one_minus_decay", C.c_float), ("ema_action", C.c_int32), ("clip_coef", C.c_float)]
 
 
 class OptimHyper(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
+class OptimHyperW(C.Structure):
+    """egoego_optim_hyper_w: decoupled weight decay and gradient clipping beside the five of OptimHyper"""
+    _fields_ = OptimHyper._fields_ + [("decoupled", C.c_int), ("max_norm", C.c_double), ("clip_eps", C.c_double)]
 
 
 class OptimEma(C.Structure):
@@ -112,7 +117,7 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_train_last_error", "egoego_train_ctx_create", "egoego_train_ctx_destroy", "egoego_train_workspace_bytes",
            "egoego_train_saves_bytes", "egoego_train_forward", "egoego_train_backward", "egoego_train_dropout_mask", "egoego_train_saved",
            "egoego_optim_last_error", "egoego_optim_ctx_create", "egoego_optim_ctx_destroy", "egoego_optim_workspace_bytes",
-           "egoego_optim_state_bytes", "egoego_optim_set_tensors", "egoego_optim_step", "egoego_optim_read_state",
+           "egoego_optim_state_bytes", "egoego_optim_set_tensors", "egoego_optim_step", "egoego_optimw_step", "egoego_optim_read_state",
            "egoego_s1_train_last_error", "egoego_s1_train_ctx_create", "egoego_s1_train_ctx_destroy", "egoego_s1_train_workspace_bytes",
            "egoego_s1_train_saves_bytes", "egoego_s1_train_forward", "egoego_s1_train_backward", "egoego_s1_train_dropout_mask",
            "egoego_s1_train_saved", "egoego_s1_headnet_loss_workspace_bytes", "egoego_s1_headnet_loss",
@@ -271,6 +276,7 @@ def load():
     # state, bytes, workspace, bytes, stream
     lib.egoego_optim_step.argtypes = [vp, C.POINTER(OptimHyper), C.POINTER(OptimEma), C.POINTER(vp), i32, vp, vp, i32, i32, i32, i32,
                                       vp, sz, vp, sz, vp]
+    lib.egoego_optimw_step.argtypes = [vp, C.POINTER(OptimHyperW)] + lib.egoego_optim_step.argtypes[2:]
     lib.egoego_optim_read_state.argtypes = [vp, vp, sz, vp, vp]
     lib.egoego_s1_train_last_error.restype = C.c_char_p
     lib.egoego_s1_train_ctx_create.argtypes = [C.POINTER(S1Config), i32, C.POINTER(vp)]

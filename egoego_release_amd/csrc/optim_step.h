@@ -5,8 +5,10 @@
 //                                  pointers, the element count, the first chunk), one Chunk entry per CHUNK elements of a tensor
 //   norm_kernel                    one workgroup per chunk: sum of (g * inv_scale)^2 in fp64, in a fixed order -> one partial
 //   decide_kernel                  one workgroup: the partials in a fixed order -> total_norm; the skip rule; the counters; this
-//                                  step's scalars (step size, sqrt of the second bias correction, the EMA action, 1 - decay)
-//   apply_kernel                   grid-stride over the chunk table: Adam, then the EMA, then the gradient's zeros
+//                                  step's scalars (step size, sqrt of the second bias correction, the EMA action, 1 - decay, and
+//                                  with clipping on clip_coef = min(1, max_norm / (total_norm + clip_eps)))
+//   apply_kernel                   grid-stride over the chunk table: Adam (L2 or decoupled weight decay; the gradient unscaled,
+//                                  then clipped, in registers only), then the EMA, then the gradient's zeros
 //
 // No float atomics and no cross-workgroup communication inside a kernel: the three launches are ordered by the stream.  Every
 // value that goes to memory is written by an ordinary vector store from plain C++.
@@ -100,6 +102,7 @@ struct Decide {
     const float* found_inf;
     int skip_nonfinite, do_adam, do_ema;
     double lr, beta1, beta2;
+    double max_norm, clip_eps;  // max_norm <= 0: no clipping
     egoego_optim_ema ema;
     egoego_optim_state* st;
 };
@@ -134,6 +137,7 @@ __global__ __launch_bounds__(THREADS) void decide_kernel(Decide a) {
     if (a.found_inf && *a.found_inf != 0.0f) skip = true;
     st.last_skip = skip ? 1 : 0;
     st.ema_action = EGOEGO_OPTIM_EMA_NONE;
+    st.clip_coef = 1.0f;
     if (skip) {
         st.skipped += 1;
     } else {
@@ -143,6 +147,10 @@ __global__ __launch_bounds__(THREADS) void decide_kernel(Decide a) {
             const double k = (double)st.adam_step;
             st.step_size = (float)(a.lr / (1.0 - pow(a.beta1, k)));
             st.bc2_sqrt = (float)sqrt(1.0 - pow(a.beta2, k));
+            if (a.max_norm > 0.0) {  // clip_grad_norm_'s coefficient, in fp64 from the fp64 norm, rounded once
+                const double coef = a.max_norm / (st.total_norm + a.clip_eps);
+                st.clip_coef = (float)(coef < 1.0 ? coef : 1.0);
+            }
         }
         if (a.do_ema) {  // ema-pytorch's update(): the decay is read after the step counter has advanced
             const int64_t step = *a.ema.d_step;
@@ -179,10 +187,12 @@ struct Apply {
     const float* inv_scale;
     float w1, beta2, w2, eps, wd;  // 1 - beta1, beta2, 1 - beta2, eps, weight decay: each rounded once from the caller's doubles
     int zero_grads;
+    float wmul;  // decoupled: (float)(1 - lr * weight_decay), formed in double
+    int decoupled, clip;
 };
 
 struct Scalars {
-    float inv, step_size, bc2_sqrt, omd;
+    float inv, step_size, bc2_sqrt, omd, clip;
     bool adam, zero;
     int action;
 };
@@ -205,7 +215,10 @@ __device__ __forceinline__ void stv(float* p, const float (&r)[W]) {
     }
 }
 
-// W elements at index i of a chunk.  torch.optim.Adam (amsgrad off; weight decay in its L2 form), then ema-pytorch's update.
+// W elements at index i of a chunk.  torch.optim.Adam (amsgrad off; weight decay in its L2 form) or, with a.decoupled,
+// torch.optim.AdamW (p *= 1 - lr * wd first, no L2 term); then ema-pytorch's update.  With a.clip the unscaled gradient is
+// multiplied by clip_coef: a second fp32 product in a statement of its own, in torch's order (unscale, then clip).  The clipped
+// value lives in registers only: the gradient in memory keeps its bits (or becomes zero).
 template <bool ADAM, bool EMA, int W>
 __device__ __forceinline__ void update(const Apply& a, const Scalars& s, float* p, float* g, float* m, float* v, float* e, long i) {
     float P[W];
@@ -219,7 +232,9 @@ __device__ __forceinline__ void update(const Apply& a, const Scalars& s, float* 
 #pragma unroll
             for (int k = 0; k < W; ++k) {
                 float gg = G[k] * s.inv;
-                if (a.wd != 0.f) gg = gg + a.wd * P[k];
+                if (a.clip) gg = gg * s.clip;
+                if (a.decoupled) P[k] = P[k] * a.wmul;
+                else if (a.wd != 0.f) gg = gg + a.wd * P[k];
                 // torch's lerp_(grad, 1 - beta1): the weight decides the form, and a weight of 1 (beta1 = 0) returns gg itself
                 const float dm = gg - M[k];
                 M[k] = a.w1 < 0.5f ? M[k] + a.w1 * dm : gg - dm * (1.0f - a.w1);
@@ -271,6 +286,7 @@ __global__ __launch_bounds__(THREADS) void apply_kernel(Apply a) {
     s.step_size = a.st->step_size;
     s.bc2_sqrt = a.st->bc2_sqrt;
     s.omd = a.st->one_minus_decay;
+    s.clip = a.st->clip_coef;
     for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
         const Chunk ch = a.chunks[c];
         const Tensor t = a.table[ch.tensor];

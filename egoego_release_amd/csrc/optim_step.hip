@@ -128,9 +128,9 @@ int egoego_optim_set_tensors(egoego_optim_ctx* ctx, float* const* p, float* cons
     return 0;
 }
 
-int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, const egoego_optim_ema* ema, const float* const* losses,
-                      int n_losses, const float* d_inv_scale, const float* d_found_inf, int skip_on, int zero_grads, int do_adam, int do_ema,
-                      void* d_state, size_t state_bytes, void* d_workspace, size_t workspace_bytes, void* stream) {
+int egoego_optimw_step(egoego_optim_ctx* ctx, const egoego_optim_hyper_w* hyper, const egoego_optim_ema* ema, const float* const* losses,
+                        int n_losses, const float* d_inv_scale, const float* d_found_inf, int skip_on, int zero_grads, int do_adam, int do_ema,
+                        void* d_state, size_t state_bytes, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_state(ctx, d_state, state_bytes)) return rc;
     if (!do_adam && !do_ema) return fail(EGOEGO_E_INVALID, "neither do_adam nor do_ema: nothing to do");
     if (do_adam && !ctx->has_adam) return fail(EGOEGO_E_INVALID, "do_adam: egoego_optim_set_tensors was not given gradients and moments");
@@ -147,6 +147,9 @@ int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, co
             !(hyper->beta2 >= 0.0 && hyper->beta2 < 1.0) || !(hyper->weight_decay >= 0.0))
             return fail(EGOEGO_E_INVALID, "lr %g, betas (%g, %g), eps %g, weight_decay %g: out of range", hyper->lr, hyper->beta1, hyper->beta2,
                         hyper->eps, hyper->weight_decay);
+        if (hyper->decoupled != 0 && hyper->decoupled != 1) return fail(EGOEGO_E_INVALID, "decoupled = %d: 0 (L2) or 1 (AdamW)", hyper->decoupled);
+        if (hyper->max_norm != hyper->max_norm) return fail(EGOEGO_E_INVALID, "max_norm is NaN (<= 0 turns clipping off)");
+        if (!(hyper->clip_eps >= 0.0)) return fail(EGOEGO_E_INVALID, "clip_eps %g: negative or NaN", hyper->clip_eps);
         if (int rc = check_workspace(d_workspace, workspace_bytes, egoego_optim_workspace_bytes(ctx))) return rc;
     }
     if (do_ema) {
@@ -176,7 +179,7 @@ int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, co
         a.skip_nonfinite = skip_on == EGOEGO_OPTIM_SKIP_NONFINITE;
         a.do_adam = do_adam != 0;
         a.do_ema = do_ema != 0;
-        if (do_adam) { a.lr = hyper->lr; a.beta1 = hyper->beta1; a.beta2 = hyper->beta2; }
+        if (do_adam) { a.lr = hyper->lr; a.beta1 = hyper->beta1; a.beta2 = hyper->beta2; a.max_norm = hyper->max_norm; a.clip_eps = hyper->clip_eps; }
         if (do_ema) a.ema = *ema;
         a.st = st;
         hipLaunchKernelGGL(op::decide_kernel, dim3(1), dim3(op::THREADS), 0, s, a);
@@ -195,6 +198,9 @@ int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, co
             a.w2 = (float)(1.0 - hyper->beta2);
             a.eps = (float)hyper->eps;
             a.wd = (float)hyper->weight_decay;
+            a.wmul = (float)(1.0 - hyper->lr * hyper->weight_decay);  // torch.optim.AdamW's param.mul_(1 - lr * weight_decay)
+            a.decoupled = hyper->decoupled;
+            a.clip = hyper->max_norm > 0.0;
         }
         a.zero_grads = zero_grads != 0;
         const dim3 grid(nch < op::MAX_BLOCKS ? nch : op::MAX_BLOCKS), block(op::THREADS);
@@ -204,6 +210,16 @@ int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, co
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, const egoego_optim_ema* ema, const float* const* losses,
+                      int n_losses, const float* d_inv_scale, const float* d_found_inf, int skip_on, int zero_grads, int do_adam, int do_ema,
+                      void* d_state, size_t state_bytes, void* d_workspace, size_t workspace_bytes, void* stream) {
+    egoego_optim_hyper_w w;
+    memset(&w, 0, sizeof w);  // decoupled = 0, max_norm = 0: the L2 form, no clipping
+    if (hyper) { w.lr = hyper->lr; w.beta1 = hyper->beta1; w.beta2 = hyper->beta2; w.eps = hyper->eps; w.weight_decay = hyper->weight_decay; }
+    return egoego_optimw_step(ctx, hyper ? &w : nullptr, ema, losses, n_losses, d_inv_scale, d_found_inf, skip_on, zero_grads, do_adam, do_ema,
+                               d_state, state_bytes, d_workspace, workspace_bytes, stream);
 }
 
 int egoego_optim_read_state(egoego_optim_ctx* ctx, const void* d_state, size_t state_bytes, egoego_optim_state* d_out, void* stream) {

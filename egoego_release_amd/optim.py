@@ -3,6 +3,7 @@ gradient clearing in one call that keeps its counters on the device and reads no
 
     UpdateEngine   one egoego_optim_ctx over a list of tensors, with its state block (counters + descriptor tables)
     FusedAdam      torch.optim.Adam's constructor, param_groups and state_dict layout in front of it
+    FusedAdamW     torch.optim.AdamW's (decoupled weight decay), with clip_grad_norm_ inside the step: stage-1 training's update
     EMA            what the reference constructs from ema-pytorch: .ema_model, .online_model, .update(), the same state_dict keys
 
 `fused=False` is the plain path of both classes: torch.optim.Adam inside and ema-pytorch's three-line lerp, on any device, with
@@ -62,6 +63,7 @@ class UpdateEngine(ContextEngine):
         self.adam_step = h[_HDR["adam_step"]:_HDR["adam_step"] + 8].view(torch.int64)
         self.last_grad_norm = h[_HDR["total_norm_f32"]:_HDR["total_norm_f32"] + 4].view(torch.float32)[0]
         self.last_skipped = h[_HDR["last_skip"]:_HDR["last_skip"] + 4].view(torch.int32)[0]
+        self.last_clip_coef = h[_HDR["clip_coef"]:_HDR["clip_coef"] + 4].view(torch.float32)[0]
 
     def _check(self, name, lst):
         for i, (t, n) in enumerate(zip(lst, self.counts)):
@@ -85,9 +87,19 @@ class UpdateEngine(ContextEngine):
             _lib.check_optim(self.lib.egoego_optim_set_tensors(self._ctx, *arrs, self.state.data_ptr(), self.state.numel(), self._stream()))
         self._ptrs = ptrs
 
-    def step(self, hyper=None, ema=None, losses=(), inv_scale=None, found_inf=None, skip_on="nan", zero_grads=False):
-        """hyper: (lr, beta1, beta2, eps, weight_decay) or None (the EMA alone); ema: an _lib.OptimEma or None."""
-        h = None if hyper is None else _lib.OptimHyper(*[float(x) for x in hyper])
+    def step(self, hyper=None, ema=None, losses=(), inv_scale=None, found_inf=None, skip_on="nan", zero_grads=False, decoupled=False,
+             max_norm=None, clip_eps=1e-6):
+        """hyper: (lr, beta1, beta2, eps, weight_decay) or None (the EMA alone); ema: an _lib.OptimEma or None.  decoupled:
+        weight_decay in torch.optim.AdamW's form; max_norm: clip_grad_norm_'s, inside the step (<= 0: none).  With neither
+        (max_norm None) the call is egoego_optim_step, else egoego_optimw_step."""
+        wide = bool(decoupled) or max_norm is not None
+        fn = self.lib.egoego_optimw_step if wide else self.lib.egoego_optim_step
+        if hyper is None:
+            h = None
+        elif wide:
+            h = _lib.OptimHyperW(*[float(x) for x in hyper], int(bool(decoupled)), 0.0 if max_norm is None else float(max_norm), float(clip_eps))
+        else:
+            h = _lib.OptimHyper(*[float(x) for x in hyper])
         losses = [l for l in losses]
         for l in losses + [t for t in (inv_scale, found_inf) if t is not None]:
             if l.device != self.device or l.dtype != torch.float32 or l.numel() != 1:
@@ -97,7 +109,7 @@ class UpdateEngine(ContextEngine):
         larr = (C.c_void_p * len(losses))(*[l.data_ptr() for l in losses]) if losses else None
         ws, wn = self._workspace() if h is not None else (None, 0)
         with torch.cuda.device(self.dev_index):
-            _lib.check_optim(self.lib.egoego_optim_step(
+            _lib.check_optim(fn(
                 self._ctx, None if h is None else C.byref(h), None if ema is None else C.byref(ema), larr, len(losses),
                 None if inv_scale is None else inv_scale.data_ptr(), None if found_inf is None else found_inf.data_ptr(),
                 _lib.OPTIM_SKIP[skip_on], int(bool(zero_grads)), int(h is not None), int(ema is not None),
@@ -125,21 +137,35 @@ class FusedAdam(torch.optim.Optimizer):
     norm or the GradScaler's found_inf skips the step on the device — parameters, moments, EMA and the step counter stay as they
     are — and nothing is read back.  `ema`: an EMA over the same model, updated in the same call.  `modules`: the nn.Modules that
     own the parameters; invalidate_engine() is called on each after every step, because the write goes through raw pointers and
-    bumps no `_version` (the sampler's packed weights would go stale)."""
+    bumps no `_version` (the sampler's packed weights would go stale).
+
+    max_grad_norm: torch.nn.utils.clip_grad_norm_(params, max_grad_norm, error_if_nonfinite=False) inside the step, after the
+    unscale.  The update uses the clipped values, but the gradients in memory are NOT rewritten with them (torch clips in place;
+    the plain path does too): after a fused step `.grad` holds what backward left, or zeros with zero_grads.  `last_grad_norm` is
+    the norm before clipping, which is what clip_grad_norm_ returns; `last_clip_coef` the factor used (1 when nothing was clipped
+    or the step was skipped).  Both are device scalars.  None (the default) is the path without clipping, unchanged."""
+
+    _TORCH, _DECOUPLED = torch.optim.Adam, False  # the optimizer whose group keys, state dict and plain path this class has
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False, fused=True,
-                 modules=(), skip_on="nan", zero_grads=False):
+                 modules=(), skip_on="nan", zero_grads=False, max_grad_norm=None):
+        name = type(self).__name__
         if amsgrad or maximize:
-            raise ValueError("FusedAdam serves amsgrad=False, maximize=False")
+            raise ValueError(f"{name} serves amsgrad=False, maximize=False")
+        if max_grad_norm is not None and not (0.0 < float(max_grad_norm) < float("inf")):
+            raise ValueError(f"max_grad_norm is None or a positive finite number, not {max_grad_norm!r}")
         if skip_on not in _lib.OPTIM_SKIP:
             raise ValueError(f"skip_on is 'nan' or 'nonfinite', not {skip_on!r}")
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not 0.0 <= weight_decay:
             raise ValueError(f"invalid lr {lr}, betas {betas}, eps {eps} or weight_decay {weight_decay}")
-        # the keys of torch.optim.Adam's groups, so that a state dict saved from one loads into the other (`fused` here is torch's)
-        defaults = dict(torch.optim.Adam([torch.zeros(1)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay).defaults)
+        # the keys of torch.optim.Adam's (AdamW's) groups, so that a state dict saved from one loads into the other (`fused` here
+        # is torch's)
+        defaults = dict(self._TORCH([torch.zeros(1)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay).defaults)
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
-            raise ValueError("FusedAdam takes one param group")
+            raise ValueError(f"{name} takes one param group")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_clip_coef = None
         self.hip = bool(fused)
         self.modules = tuple(modules)
         self.skip_on, self.zero_grads = skip_on, bool(zero_grads)
@@ -160,7 +186,7 @@ class FusedAdam(torch.optim.Optimizer):
     def _grads(self, params):
         for p in params:
             if p.grad is None:
-                raise RuntimeError("FusedAdam.step(): a parameter that requires a gradient has none; run backward before the first step")
+                raise RuntimeError(f"{type(self).__name__}.step(): a parameter that requires a gradient has none; run backward before the first step")
         return [p.grad for p in params]
 
     def zero_grad(self, set_to_none=False):
@@ -174,7 +200,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     # ------------------------------------------------------------------ the plain path
     def _make_plain(self):
-        self._plain = torch.optim.Adam(self.param_groups[0]["params"], foreach=False)
+        self._plain = self._TORCH(self.param_groups[0]["params"], foreach=False)
         self._plain.param_groups, self._plain.state = self.param_groups, self.state
 
     def _step_plain(self, ema, losses):
@@ -197,6 +223,9 @@ class FusedAdam(torch.optim.Optimizer):
             self._host["skipped"] += 1
         else:
             self._host["applied"] += 1
+            if self.max_grad_norm is not None:  # in place, as torch does: the plain path leaves clipped gradients behind
+                torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm, error_if_nonfinite=False, foreach=False)
+                self.last_clip_coef = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
             self._plain.step()
             if ema is not None:
                 ema.update()
@@ -214,6 +243,7 @@ class FusedAdam(torch.optim.Optimizer):
                                           "fused=False is the plain path")
             self._engine = UpdateEngine([p.numel() for p in params], dev)
             self.last_grad_norm, self.last_skipped = self._engine.last_grad_norm, self._engine.last_skipped
+            self.last_clip_coef = self._engine.last_clip_coef
             self._push_step()
         return self._engine
 
@@ -274,7 +304,7 @@ class FusedAdam(torch.optim.Optimizer):
         found = getattr(self, "found_inf", None)
         eng.step((g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]), None if ema is None else ema._schedule(),
                  [l.detach().reshape(()) for l in (losses or ())], inv, None if found is None else found.reshape(()),
-                 self.skip_on, self.zero_grads)
+                 self.skip_on, self.zero_grads, self._DECOUPLED, self.max_grad_norm)
         _invalidate(self.modules)
         if ema is not None:
             _invalidate([ema.ema_model])
@@ -308,6 +338,20 @@ class FusedAdam(torch.optim.Optimizer):
             self._push_step()
         else:
             self._plain.param_groups, self._plain.state = self.param_groups, self.state
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW (amsgrad off) on the same fused call: p *= 1 - lr * weight_decay first, then Adam without the L2 term;
+    torch.optim.AdamW's constructor (weight_decay = 1e-2), group keys and state dict, so a state dict goes either way.  One param
+    group.  `lr` is read from param_groups[0] at every step, so torch's lr schedulers (StepLR) drive it unchanged.  fused=False is
+    the unscale, clip_grad_norm_(error_if_nonfinite=False) and torch.optim.AdamW(foreach=False), under FusedAdam's skip rule."""
+
+    _TORCH, _DECOUPLED = torch.optim.AdamW, True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, fused=True,
+                 modules=(), skip_on="nan", zero_grads=False, max_grad_norm=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize, fused=fused, modules=modules, skip_on=skip_on,
+                         zero_grads=zero_grads, max_grad_norm=max_grad_norm)
 
 
 class EMA(nn.Module):

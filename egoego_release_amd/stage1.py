@@ -229,6 +229,11 @@ class _Stage1Module(nn.Module):
         # state_dict() would carry the bound method, and with it the whole module, into every checkpoint)
         return tuple((p.data_ptr(), p._version) for p in self.state_dict().values())
 
+    def invalidate_engine(self):
+        """For an optimizer that writes the parameters through raw pointers (optim.FusedAdamW): no `_version` moves, so the
+        inference engine's packed copy is declared stale here.  The training engine reads the live parameters and needs nothing."""
+        self._packed = None
+
     def train_engine(self):
         """The training engine (egoego_s1_train_*), on the device of the parameters."""
         from .stage1_train import Stage1TrainEngine

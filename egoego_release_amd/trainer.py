@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import harness
-from .optim import EMA, FusedAdam
+from .optim import EMA, FusedAdam, FusedAdamW
 from .synthetic import head_condition_mask
 
 
@@ -177,19 +177,29 @@ class Stage1Trainer:
     run would have).
 
     The model is a stage1.HeadFormer or stage1.HeadNormalFormer with its parameters on the GPU; the trainer sets hip_training (the
-    gradients come from egoego_s1_train_backward) and train() mode.  The update is torch.optim.AdamW: optim.FusedAdam has neither
-    decoupled weight decay nor clipping.  Nothing is read back from the device inside an epoch; `history` holds one dict of epoch
-    means (device work done once per epoch), `val_history` the validation means."""
+    gradients come from egoego_s1_train_backward) and train() mode.  The update is clip_grad_norm_ and torch.optim.AdamW by default.
+    fused_update=True makes it optim.FusedAdamW(max_grad_norm=max_grad_norm, zero_grads=True, skip_on="nonfinite"): norm, clip,
+    decoupled decay, Adam and the gradients' zeros in three launches, with the same scheduler, history and checkpoint keys
+    ('optimizer_state_dict' in AdamW's layout: a checkpoint of either path resumes under the other).  Two differences from the
+    default path: the gradients are not rewritten with their clipped values (they are cleared), and a step whose gradient norm is
+    not finite is skipped on the device (the parameters, moments and step counter stay), where the reference, like the default
+    path, would multiply every gradient by NaN and fill the net with it.  Nothing is read back from the device inside an epoch;
+    `history` holds one dict of epoch means (device work done once per epoch), `val_history` the validation means."""
 
     def __init__(self, model, train_batches, val_batches=None, *, lr=1e-4, step_size=None, gamma=0.3, validation_iter=1,
-                 save_interval=50, save_dir="./results", val_batches_max=50, max_grad_norm=1.0):
+                 save_interval=50, save_dir="./results", val_batches_max=50, max_grad_norm=1.0, fused_update=False):
         self.model = model
         self.train_batches, self.val_batches = train_batches, val_batches
         self.headnet = model.cfg.kind == "headnet"
         self.keys = ("loss", "orient", "va", "dist") if self.headnet else ("loss", "normal")
         model.hip_training = True
         model.train()
-        self.optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
+        self.fused_update = bool(fused_update)
+        if self.fused_update:
+            self.optimizer = FusedAdamW(model.parameters(), lr=lr, max_grad_norm=max_grad_norm, modules=(model,), zero_grads=True,
+                                        skip_on="nonfinite")
+        else:
+            self.optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
         if step_size is None:
             step_size = 1000 if self.headnet else 2000
         self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=step_size, gamma=gamma)
@@ -226,7 +236,8 @@ class Stage1Trainer:
         parts = self.model.compute_loss(out, batch)
         self.optimizer.zero_grad()
         parts[0].backward()
-        torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm, error_if_nonfinite=False)
+        if not self.fused_update:  # (the fused step clips)
+            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm, error_if_nonfinite=False)
         self.optimizer.step()
         self.last_loss = parts[0].detach()
         return tuple(p.detach() for p in parts)

@@ -734,11 +734,27 @@ typedef struct {
     float bc2_sqrt;         /* sqrt(1 - beta2^step) */
     float one_minus_decay;  /* of the last lerp */
     int32_t ema_action;     /* EGOEGO_OPTIM_EMA_* of the last call */
+    float clip_coef;        /* min(1, max_norm / (total_norm + clip_eps)) of the last call; 1 without clipping or when skipped */
 } egoego_optim_state;
 
 typedef struct {
     double lr, beta1, beta2, eps, weight_decay;  /* weight_decay: torch's L2 form, g + weight_decay * p */
 } egoego_optim_hyper;
+
+/* egoego_optimw_step's hyper-parameters: the five above, then
+ *   decoupled  0: weight_decay is the L2 term.  1: torch.optim.AdamW's form, p *= (float)(1 - lr * weight_decay) (the factor
+ *              formed in double, rounded once) before an Adam step without the L2 term;
+ *   max_norm   > 0: torch.nn.utils.clip_grad_norm_ inside the step.  decide computes coef = min(1, max_norm / (total_norm +
+ *              clip_eps)) in fp64 from the fp64 norm and rounds it once to egoego_optim_state.clip_coef; the update uses
+ *              (g * inv_scale) * clip_coef, two fp32 products in torch's order.  The gradients in memory are NOT rewritten
+ *              with their clipped values (torch clips in place): they keep their bits, or are cleared by zero_grads.
+ *              <= 0: no clipping; NaN is refused;
+ *   clip_eps   clip_grad_norm_'s 1e-6; >= 0. */
+typedef struct {
+    double lr, beta1, beta2, eps, weight_decay;
+    int decoupled;
+    double max_norm, clip_eps;
+} egoego_optim_hyper_w;
 
 /* ema-pytorch's schedule: a call with do_ema reads *d_step, adds one, and acts only when the value it read is a multiple of
  * update_every: a copy up to update_after_step and, once, on the first call after it (which sets *d_initted = 1); afterwards
@@ -767,6 +783,12 @@ int egoego_optim_set_tensors(egoego_optim_ctx* ctx, float* const* p, float* cons
 int egoego_optim_step(egoego_optim_ctx* ctx, const egoego_optim_hyper* hyper, const egoego_optim_ema* ema, const float* const* losses,
                       int n_losses, const float* d_inv_scale, const float* d_found_inf, int skip_on, int zero_grads, int do_adam, int do_ema,
                       void* d_state, size_t state_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
+/* egoego_optim_step with decoupled weight decay and gradient clipping (egoego_optim_hyper_w); the same three launches, and
+ * nothing else differs.  egoego_optim_step is this call with decoupled = 0, max_norm = 0.  A bad decoupled, a NaN max_norm or a
+ * negative clip_eps is refused before any launch. */
+int egoego_optimw_step(egoego_optim_ctx* ctx, const egoego_optim_hyper_w* hyper, const egoego_optim_ema* ema, const float* const* losses,
+                        int n_losses, const float* d_inv_scale, const float* d_found_inf, int skip_on, int zero_grads, int do_adam, int do_ema,
+                        void* d_state, size_t state_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
 /* Copies the egoego_optim_state at the head of d_state to d_out (device memory) on `stream`: the one call a caller may follow with
  * a synchronisation, to read counters for tests and logging. */
 int egoego_optim_read_state(egoego_optim_ctx* ctx, const void* d_state, size_t state_bytes, egoego_optim_state* d_out, void* stream);

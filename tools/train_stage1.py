@@ -54,6 +54,8 @@ def parse_opt(argv=None):
     p.add_argument("--w_dist", type=float, default=1.0)
     p.add_argument("--dist_scale", type=float, default=10.0)
     p.add_argument("--resume", default=None, help="a checkpoint to continue from")
+    p.add_argument("--fused_update", action="store_true",
+                   help="clip + AdamW in one fused call (optim.FusedAdamW); a step with a non-finite gradient norm is skipped")
     p.add_argument("--device", default="cuda")
     opt = p.parse_args(argv)
     if opt.window is None:
@@ -106,7 +108,7 @@ def main(argv=None):
         train = [make_stage1_train_batch(opt.kind, opt.batch_size, opt.window, seed=s) for s in range(opt.synthetic_batches)]
         val = [make_stage1_train_batch(opt.kind, opt.batch_size, opt.window, seed=10_000 + s) for s in range(2)]
     tr = Stage1Trainer(model, train, val, lr=opt.learning_rate, validation_iter=opt.validation_iter, save_interval=opt.save_interval,
-                       save_dir=opt.save_dir)
+                       save_dir=opt.save_dir, fused_update=opt.fused_update)
     if opt.resume:
         tr.load(opt.resume)
     os.makedirs(opt.save_dir, exist_ok=True)
