@@ -87,7 +87,10 @@ struct TailArgs {
 };
 
 static constexpr int tail_smem_bytes(int TT, int NWV = 4) { return TT * 32 * 1024 + 3 * TT * NWV * 32 * TT * 4; }  // chunk double buffer + epilogue scratch
-static constexpr int TAIL_PAR_BYTES = 10 * 512 * 4;  // the all-int8 build also stages its ten per-feature parameter vectors in LDS
+// the all-int8 build also stages its ten per-feature parameter vectors in LDS, and behind them the block's attention-output row
+// scales (at most 64 tokens x 16 heads)
+static constexpr int TAIL_PAR_FLOATS = 10 * 512, TAIL_OSC_FLOATS = 64 * 16;
+static constexpr int TAIL_PAR_BYTES = (TAIL_PAR_FLOATS + TAIL_OSC_FLOATS) * 4;
 
 // Weight / activation fragments are fetched through buffer resources: address = SGPR base + SGPR offset + one VGPR
 // (plain global loads make hipcc build a 64-bit VGPR address per fragment and k-step: hundreds of registers of them).
@@ -111,7 +114,9 @@ EG_D i32x4 tail_load(tail_rsrc r, int voff, unsigned soff) {
 // one MFMA group that uses it; each fragment is consumed >= FT*TT MFMAs after its read was issued.
 // I8 = true: the operands are int8 slices (k-blocks of 32; "hi" plane = slice 1, "lo" plane = slice 2) and the sums go to
 // an I8Acc pair — s2*s1 and s1*s2 into .m, s1*s1 into .h, the groups in the order of the split-bf16 parts.
-template <int FT, int TT, int RING, bool LAST, int DP, int NKS = 8, bool I8 = false, bool WLO0 = false>
+// DMAWAIT = false: run() leaves the wait for the next chunk's pieces to the caller (DirectGemm::run_heads, where several
+// runs share one LDS chunk and the pieces have all of them to land).
+template <int FT, int TT, int RING, bool LAST, int DP, int NKS = 8, bool I8 = false, bool WLO0 = false, bool DMAWAIT = true>
 struct TailChunk {
     using AccT = typename std::conditional<I8, I8Acc, f32x16>::type;
     static constexpr int PD = RING - 1, NW = FT * 2;  // NKS < 8: the short last chunk of a contraction whose k-blocks are no multiple of 8
@@ -120,7 +125,11 @@ struct TailChunk {
     static_assert(!WLO0 || I8, "int8 slices only");
     static_assert(NKS == 8 || (LAST && DP == 0), "only the last chunk may be short");
     static_assert(RING == 2 || RING == 4 || RING == 8, "ring slots must divide the 8 k-steps of a chunk");
-    static constexpr int n_ops(int s) { return ((s + PD < NKS || !LAST) ? NWL : 0) + (s == 0 ? DP : 0); }
+    // what k-step s issues to the vector-memory queue, in this order: the weight fragments of k-step s + PD, then the DMA pieces
+    // (step() issues by these very predicates, and so does the queue model that checks the counted waits: FcQueueModel)
+    static constexpr bool loads_at(int s) { return s + PD < NKS || !LAST; }
+    static constexpr int dma_at(int s) { return s == 0 ? DP : 0; }
+    static constexpr int n_ops(int s) { return (loads_at(s) ? NWL : 0) + dma_at(s); }
     // vector-memory operations issued after the DMA pieces: what may stay in flight when the next chunk must have landed
     static constexpr int after_dma() {
         int n = 0;
@@ -160,15 +169,15 @@ struct TailChunk {
         asm volatile("" ::: "memory");
         wait_counts<allowed(KS), (KS == 0 ? 0 : TT)>();
         __builtin_amdgcn_sched_barrier(0);
-        if (KS + PD < NKS || !LAST) {
+        if (loads_at(KS)) {
             constexpr int kn = KS + PD;
 #pragma unroll
             for (int q = 0; q < NW; ++q)
                 if (!(TAIL_ABLATE & 1) && !(WLO0 && (q & 1))) wq[kn % RING][q] = tail_load(wr, lane * 16, kn < 8 ? wcur[q] + (kn << 10) : wnext[q] + ((kn & 7) << 10));
         }
-        if (KS == 0 && DP) {
+        if (dma_at(KS)) {
 #pragma unroll
-            for (int d = 0; d < DP; ++d)
+            for (int d = 0; d < dma_at(KS); ++d)
                 if (!(TAIL_ABLATE & 4)) dma(d);
         }
         if (KS < NKS - 1) {
@@ -224,10 +233,59 @@ struct TailChunk {
         if (NKS > 5) step<5>(acc, wq, ah, al, wr, wcur, wnext, act, act_plane, lane, dma);
         if (NKS > 6) step<6>(acc, wq, ah, al, wr, wcur, wnext, act, act_plane, lane, dma);
         if (NKS > 7) step<7>(acc, wq, ah, al, wr, wcur, wnext, act, act_plane, lane, dma);
-        if (DP) {  // the next chunk has landed; the weight prefetches issued after its pieces stay in flight
+        if (DP && DMAWAIT) {  // the next chunk has landed; the weight prefetches issued after its pieces stay in flight
             asm volatile("" ::: "memory");
             wait_counts<after_dma(), 15>();
         }
+    }
+};
+
+// ---- the counted waits of the head-major fc (DirectGemm::run_heads), checked when the kernel is compiled --------------
+// A constexpr replay of one wave's vector-memory queue over a whole contraction of NH heads x FP feature passes: every
+// operation gets its position in the queue, in the order run_heads and TailChunk::step issue them (the predicates loads_at /
+// dma_at are the ones step() itself branches on).  Loads return in order, so `s_waitcnt vmcnt(N)` lets the N youngest
+// stay in flight: a wait is right when the awaited load has at least N younger ones behind it, and tight when it has
+// exactly N (or more than the counter's 63).  check() returns 0 when every wait of the contraction is tight, else 1 + the
+// index of the first one that is not — run_heads static_asserts on it, so a miscounted table does not compile.
+template <int FT, int TT, int RING, int DP, bool I8, bool WLO0, int FP, int NH>
+struct FcQueueModel {
+    using First = TailChunk<FT, TT, RING, false, DP, 8, I8, WLO0, false>;  // segment (h, 0) of a head with a successor: requests the next chunk
+    using Mid = TailChunk<FT, TT, RING, false, 0, 8, I8, WLO0>;            // every other segment but the closing one
+    using Last = TailChunk<FT, TT, RING, true, 0, 8, I8, WLO0>;            // the closing segment: prefetches nothing
+    static constexpr int PD = RING - 1, NWL = First::NWL, NSEG = NH * FP;
+    static constexpr int clamp63(int n) { return n < 63 ? n : 63; }
+    static constexpr int check(int dma_wait) {
+        int issued = 0, waits = 0;
+        int w_end[NSEG + 1][8] = {};  // queue length right behind the weight fragments of (segment, k-step)
+        int d_end[NH + 1] = {};       // ... behind the DMA pieces of chunk h
+        issued += DP;                 // prologue: the first chunk's pieces, then the first PD k-steps of weights; vmcnt(0)
+        d_end[0] = issued;
+        for (int k = 0; k < PD; ++k) {
+            issued += NWL;
+            w_end[0][k] = issued;
+        }
+        for (int seg = 0; seg < NSEG; ++seg) {
+            const int h = seg / FP, fp = seg % FP;
+            const bool last = seg == NSEG - 1, first = fp == 0 && h + 1 < NH;
+            for (int ks = 0; ks < 8; ++ks) {
+                const int n = last ? Last::allowed(ks) : (first ? First::allowed(ks) : Mid::allowed(ks));
+                ++waits;
+                if (n != clamp63(issued - w_end[seg][ks])) return waits;
+                if (last ? Last::loads_at(ks) : (first ? First::loads_at(ks) : Mid::loads_at(ks))) {
+                    issued += NWL;
+                    w_end[ks + PD < 8 ? seg : seg + 1][(ks + PD) & 7] = issued;
+                }
+                if (first && First::dma_at(ks)) {
+                    issued += First::dma_at(ks);
+                    d_end[h + 1] = issued;
+                }
+            }
+            if (fp == FP - 1 && h + 1 < NH) {  // the head's closing wait: chunk h + 1 has landed
+                ++waits;
+                if (dma_wait != clamp63(issued - d_end[h + 1])) return waits;
+            }
+        }
+        return 0;
     }
 };
 
@@ -316,6 +374,86 @@ struct DirectGemm {
         __syncthreads();  // every wave is done with the chunk buffers before the next GEMM's first DMA
     }
 
+    // The int8 fc of the builds whose wave runs its feature tiles in FP passes of FT (this struct's FT is one pass's share),
+    // HEAD-MAJOR: for head h: for pass fp: the 8 k-steps of head h's chunk (one chunk = one head's 8 k-blocks) on the tiles of
+    // pass fp, then post(h, fp) folds the pass's integer sums away.  Every chunk goes L2 -> LDS ONCE (run() per pass would stream
+    // the operand FP times, with a pipeline fill per pass); chunk h + 1 is requested at the start of head h and has FP * 8 k-steps to
+    // land; one barrier per head.  The weight ring stays full across all NQ * FP segments: a segment's last PD k-steps prefetch
+    // the first k-blocks of the NEXT segment's tiles (wnext).  Per output element: the same integer chain per head and the
+    // folds with h ascending, as in run(): same bits.  post must issue no vector-memory operation (the counted waits).
+    template <int FP>
+    static constexpr int heads_dma_wait() {  // issued behind a chunk's pieces when the head closes: 7 k-steps of pass 0 + 8 of each other pass
+        constexpr int n = (7 + 8 * (FP - 1)) * (WLO0 ? FT : NW);
+        return n < 63 ? n : 63;
+    }
+    template <int FP, int fp, bool LASTH, class Post, class Dma>
+    static EG_D void head_passes(AccT (&q)[FT][TT], i32x4 (&wq)[RING][NW], tail_rsrc wr, unsigned wpb, int K16, int wtile0, int h, const char* buf, int lane,
+                                 Post& post, Dma dma) {
+        auto w_offsets = [&](int p, int kb, unsigned (&out)[NW]) {
+#pragma unroll
+            for (int i = 0; i < FT; ++i)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) out[2 * i + s] = s * wpb + (unsigned)(((wtile0 + p * FT + i) * K16 + kb) << 10);
+        };
+        unsigned wcur[NW], wnext[NW];
+        w_offsets(fp, 8 * h, wcur);
+        if (fp + 1 < FP) w_offsets(fp + 1, 8 * h, wnext);
+        else w_offsets(0, 8 * h + 8, wnext);
+        if constexpr (LASTH && fp == FP - 1) TailChunk<FT, TT, RING, true, 0, 8, I8, WLO0>::run(q, wq, wr, wcur, wcur, buf, CH_PLANE, lane, [](int) {});
+        else if constexpr (!LASTH && fp == 0) TailChunk<FT, TT, RING, false, DMA_PIECES, 8, I8, WLO0, false>::run(q, wq, wr, wcur, wnext, buf, CH_PLANE, lane, dma);
+        else TailChunk<FT, TT, RING, false, 0, 8, I8, WLO0>::run(q, wq, wr, wcur, wnext, buf, CH_PLANE, lane, [](int) {});
+        post(h, std::integral_constant<int, fp>{});
+        if constexpr (fp + 1 < FP) head_passes<FP, fp + 1, LASTH>(q, wq, wr, wpb, K16, wtile0, h, buf, lane, post, dma);
+    }
+    template <int FP, class Mark, class Post, class Pre>
+    static EG_D void run_heads(AccT (&q)[FT][TT], const __bf16* in, size_t in_plane, int K16, const __bf16* w, size_t w_plane, char* act, int tt0, int wave,
+                               int lane, Mark mark, int wtile0, Post post, Pre pre) {
+        static_assert(I8 && !REM2 && FP > 1, "the int8 fc in several feature passes");
+        static_assert(FcQueueModel<FT, TT, RING, DMA_PIECES, I8, WLO0, FP, 1>::check(heads_dma_wait<FP>()) == 0 &&
+                          FcQueueModel<FT, TT, RING, DMA_PIECES, I8, WLO0, FP, 2>::check(heads_dma_wait<FP>()) == 0 &&
+                          FcQueueModel<FT, TT, RING, DMA_PIECES, I8, WLO0, FP, 4>::check(heads_dma_wait<FP>()) == 0,
+                      "a counted wait of the head-major fc does not match the order its loads are issued in");
+        i32x4 wq[RING][NW];
+        const tail_rsrc wr = tail_make_rsrc(w, w_plane * 4);
+        const tail_rsrc ir = tail_make_rsrc((const char*)in + (((size_t)tt0 * (size_t)K16) << 10), 0x7fffffffu);  // based at this workgroup's rows, as in run()
+        const unsigned wpb = (unsigned)(w_plane * 2), ipb = (unsigned)(in_plane * 2);
+        const int NQ = K16 / 8;  // heads
+        auto dma_piece = [&](int c, int piece) {
+            const int x = wave * DMA_PIECES + piece;  // flat index over [plane][t-tile][8 k-blocks]
+            const int s = x / (8 * TT), j = (x >> 3) % TT, kb = x & 7;
+            const unsigned src = s * ipb + (unsigned)((j * K16 + 8 * c + kb) << 10);
+            char* dst = act + (c & 1) * CH_BYTES + s * CH_PLANE + ((j * 8 + kb) << 10);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ir, (__attribute__((address_space(3))) void*)dst, 16, lane * 16, src, 0, 0);
+        };
+#pragma unroll
+        for (int pc = 0; pc < DMA_PIECES; ++pc) dma_piece(0, pc);
+#pragma unroll
+        for (int k = 0; k < PD; ++k)
+#pragma unroll
+            for (int i = 0; i < FT; ++i)
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+                    if (!(WLO0 && s)) wq[k][2 * i + s] = tail_load(wr, lane * 16, s * wpb + (unsigned)(((wtile0 + i) * K16 + k) << 10));
+#pragma unroll
+        for (int i = 0; i < FT; ++i)
+#pragma unroll
+            for (int j = 0; j < TT; ++j) acc_zero(q[i][j]);
+        pre();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        mark();
+        for (int h = 0; h + 1 < NQ; ++h) {
+            head_passes<FP, 0, false>(q, wq, wr, wpb, K16, wtile0, h, act + (h & 1) * CH_BYTES, lane, post, [&](int piece) { dma_piece(h + 1, piece); });
+            // chunk h + 1 has landed (the weight prefetches issued behind its pieces stay in flight) and everyone is done with chunk h
+            asm volatile("" ::: "memory");
+            wait_counts<heads_dma_wait<FP>(), 15>();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+        head_passes<FP, 0, true>(q, wq, wr, wpb, K16, wtile0, NQ - 1, act + ((NQ - 1) & 1) * CH_BYTES, lane, post, [](int) {});
+        __syncthreads();  // every wave is done with the chunk buffers before the next GEMM's first DMA
+    }
+
     // The same contraction with the WHOLE activation operand already in LDS: K = 16 k-blocks of 32 (the 512-wide int8 rows of
     // the FFN contractions) are exactly the two chunk buffers, written there by the previous epilogue (gemm.h lds_chunk_slot)
     // instead of going to memory and coming back by LDS-DMA.  No DMA, no barrier inside: the caller's barrier after the
@@ -367,6 +505,10 @@ struct DirectGemm {
 // lone workgroup's weight stream is latency-bound (bytes in flight / L2 latency): a second resident workgroup doubles the bytes
 // in flight and fills the other's epilogues.  Every contraction then runs its 4 feature tiles per wave in two passes of 2
 // (I8Acc pairs of 2 tiles + a 4-slot weight ring = 128 registers); integer sums and float operations are unchanged: same bits.
+// fc runs its two passes HEAD-MAJOR (DirectGemm::run_heads): both on head h's chunk while it is in LDS — the attention output
+// is streamed once, not once per pass (measured at B=256: 48 MB less fetched from beyond L2 per launch, tail -2.5 .. -5 %,
+// profiles/tail_head_major_ab.md).  Raised wave priority (s_setprio 1 / 2 / 3) around the three epilogues, and the opposite
+// assignment, measured inside the noise and is not here.
 // NWV = 8 (int8 fc + FFN only): ONE eight-wave workgroup per CU, two 256-register waves per SIMD, a wave owning 64 features — for grids
 // of at most one workgroup per CU (every shard of the 8- and 4-GPU splits of BASELINE configs[2]), where a workgroup is a serial
 // chain and the chip is not full: a SIMD's second wave issues its weight loads and MFMAs in the first one's waits, and the three
@@ -422,6 +564,13 @@ __global__ __launch_bounds__(64 * NWV, ((W2 || NWV == 8) ? 2 : 1)) void tail_ker
         if (threadIdx.x < 128) {
 #pragma unroll
             for (int v = 0; v < 10; ++v) *(float4*)(par + v * 512 + 4 * threadIdx.x) = *(const float4*)(par_src[v] + 4 * threadIdx.x);
+            // ... and the block's attention-output row scales (32 TT tokens x H heads, contiguous in o_scale; head-major in LDS, so
+            // that the lanes of a fold read consecutive words): fc's folds read them from LDS — a global load inside fc's loop is
+            // waited for with vmcnt, which is in order: it drained the weight ring
+            if constexpr (FC8) {
+                const float* const src = a.o_scale + (size_t)tok0 * a.H;
+                for (int x = threadIdx.x; x < TOK * a.H; x += 128) par[TAIL_PAR_FLOATS + (x % a.H) * TOK + x / a.H] = src[x];
+            }
         }
     };
     if constexpr (FFN8 && FC8) {
@@ -436,63 +585,59 @@ __global__ __launch_bounds__(64 * NWV, ((W2 || NWV == 8) ? 2 : 1)) void tail_ker
     if constexpr (FC8) {
         // One exact integer chain per head (8 k-blocks = one chunk), folded into the fp32 running sum `acc` between chains.
         // A wave's 4 feature tiles go in FP passes of 4 / FP tiles: with 64 tokens per workgroup (TT = 2) the I8Acc pairs of
-        // all 8 tiles next to their 8 running-sum tiles would exceed the register file, so the two feature halves run one
-        // after the other (the activation chunks are streamed twice, the weights once either way).
+        // all 8 tiles next to their 8 running-sum tiles would exceed the register file, and the 256-register builds have room
+        // for the pairs of 2 tiles.  The passes run head-major (DirectGemm::run_heads): both on the chunk of head h while it sits
+        // in LDS, so the attention output is streamed once, as the weights are.
         constexpr int FP = NWV == 8 ? 1 : ((W2 || TAIL_RING1 == 8) ? 2 : TT), FTP = FT / FP;
-        using GF = DirectGemm<FTP, TT, (NWV == 8 ? TAIL8_RING_FC : (W2 ? 4 : TAIL_RING1)), false, true, NWV>;
-        const int col = lane & 31;
+        constexpr int RING_FC = NWV == 8 ? TAIL8_RING_FC : (W2 ? 4 : TAIL_RING1);
+        EG_DBG(unsigned long long fold_ticks = 0;)  // shader clock ticks wave 0 spent in the folds (trace slot 10)
+        const float* const osc = (const float*)(smem + tail_smem_bytes(TT, NWV)) + TAIL_PAR_FLOATS + (lane & 31);  // [head][token] row scales, this lane's token (stage_params)
 #pragma unroll
         for (int i = 0; i < FT; ++i)
 #pragma unroll
             for (int j = 0; j < TT; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#pragma unroll
-        for (int fp = 0; fp < FP; ++fp) {
-            I8Acc q[FTP][TT];
-            GF::run(q, (const __bf16*)a.o8, a.o8_plane / 2, a.HD16 / 2, (const __bf16*)a.wfc8, a.wfc8_plane / 2, act, tt0, wave, lane, [&] { mark(7); },
-                    wave * FT + fp * FTP, [&](int h) {  // head h's chain is complete: fold it into the running sum, start the next from zero
-                        float so[TT];
-#pragma unroll
-                        for (int j = 0; j < TT; ++j) so[j] = a.o_scale[(size_t)(tok0 + j * 32 + col) * a.H + h] * 256.0f;
-#pragma unroll
-                        for (int i = 0; i < FTP; ++i)
-#pragma unroll
-                            for (int j = 0; j < TT; ++j) {
-                                i8_fold(q[i][j], acc[fp * FTP + i][j], so[j]);
-                                acc_zero(q[i][j]);
-                            }
-                    }, [&] { if (fp == 0) stage_params(); });
-        }
-        // EGOEGO_FLAG_FC24: a second contraction per feature pass with the weights' THIRD slice (w ~ scale (q16 + w3 / 256)): the same
-        // chain with [w3 | 0] as the weight slices gives 256 sum(w3 a1) + sum(w3 a2), worth 1 / 65536 of the first pass's units.
+        // WLO0 = false: the contraction with w_fc's two leading slices.  true — EGOEGO_FLAG_FC24: a second contraction with the weights'
+        // THIRD slice (w ~ scale (q16 + w3 / 256)): the same chain with [w3 | 0] as the weight slices gives 256 sum(w3 a1) + sum(w3 a2),
+        // worth 1 / 65536 of the first one's units.
         // (Round 4: on the trained-like checkpoint fc on the 16-bit weight grid is what separates precision 9 from 8 at the end of a
         // whole chain — 7.0e-4 against 4.3e-4 with this pass, 3.1e-4 in precision 8.  The all-zero second weight slice is neither loaded
         // nor multiplied: DirectGemm's WLO0 form, two MFMAs per product.)
-        if (a.wfc8_3) {
+        auto fc_slices = [&](auto wlo0, const int8_t* w8, float unit, auto mark7, auto pre) {
+            using GF = DirectGemm<FTP, TT, RING_FC, false, true, NWV, decltype(wlo0)::value>;
+            I8Acc q[FTP][TT];
+            // head h's chain of pass fp is complete: fold it into the running sum, start the next from zero
+            auto fold = [&](int h, auto fpc) {
+                constexpr int fp = decltype(fpc)::value;
+                EG_DBG(const unsigned long long c0 = __builtin_readcyclecounter();)
+                float so[TT];
 #pragma unroll
-            for (int fp = 0; fp < FP; ++fp) {
-                I8Acc q[FTP][TT];
-                using GF3 = DirectGemm<FTP, TT, (NWV == 8 ? TAIL8_RING_FC : (W2 ? 4 : TAIL_RING1)), false, true, NWV, true>;  // second weight slice: zero, skipped
-                GF3::run(q, (const __bf16*)a.o8, a.o8_plane / 2, a.HD16 / 2, (const __bf16*)a.wfc8_3, a.wfc8_plane / 2, act, tt0, wave, lane, [&] {},
-                        wave * FT + fp * FTP, [&](int h) {
-                            float so[TT];
+                for (int j = 0; j < TT; ++j) so[j] = osc[h * TOK + j * 32] * unit;
 #pragma unroll
-                            for (int j = 0; j < TT; ++j) so[j] = a.o_scale[(size_t)(tok0 + j * 32 + col) * a.H + h] * (1.0f / 256.0f);
+                for (int i = 0; i < FTP; ++i)
 #pragma unroll
-                            for (int i = 0; i < FTP; ++i)
-#pragma unroll
-                                for (int j = 0; j < TT; ++j) {
-                                    i8_fold(q[i][j], acc[fp * FTP + i][j], so[j]);
-                                    acc_zero(q[i][j]);
-                                }
-                        });
+                    for (int j = 0; j < TT; ++j) {
+                        i8_fold(q[i][j], acc[fp * FTP + i][j], so[j]);
+                        acc_zero(q[i][j]);
+                    }
+                EG_DBG(fold_ticks += __builtin_readcyclecounter() - c0;)
+            };
+            if constexpr (FP > 1) {
+                GF::template run_heads<FP>(q, (const __bf16*)a.o8, a.o8_plane / 2, a.HD16 / 2, (const __bf16*)w8, a.wfc8_plane / 2, act, tt0, wave, lane, mark7,
+                                           wave * FT, fold, pre);
+            } else {
+                GF::run(q, (const __bf16*)a.o8, a.o8_plane / 2, a.HD16 / 2, (const __bf16*)w8, a.wfc8_plane / 2, act, tt0, wave, lane, mark7, wave * FT,
+                        [&](int h) { fold(h, std::integral_constant<int, 0>{}); }, pre);
             }
-        }
+        };
+        fc_slices(std::false_type{}, a.wfc8, 256.0f, [&] { mark(7); }, [&] { stage_params(); });
+        if (a.wfc8_3) fc_slices(std::true_type{}, a.wfc8_3, 1.0f / 256.0f, [] {}, [] {});
 #pragma unroll
         for (int i = 0; i < FT; ++i)
 #pragma unroll
             for (int j = 0; j < TT; ++j) i8_fold_finish(acc[i][j], p_swfc + wave * FT * 32 + i * 32 + 4 * (lane >> 5));
+        EG_DBG(if (tr && threadIdx.x == 0) tr[10] = fold_ticks;)
     } else {
         G::run(acc, a.o, a.o_plane, a.HD16, a.wfc, a.wfc_plane, act, tt0, wave, lane, [&] { mark(7); });
     }
