@@ -272,7 +272,9 @@ __global__ void __launch_bounds__(MT_THREADS) eval_metrics_kernel(MetricArgs a) 
             tot[q] = v;
         }
         double* o = a.out + (size_t)b * N_METRICS;
-        const double n = (double)L, na = (double)(L - 2);
+        // below 3 frames no frame has both neighbours: the reference takes np.mean of nothing, NaN (0 / 0 here; L - 2 would
+        // give 0 / -1 = -0.0 at L = 1)
+        const double n = (double)L, na = L > 2 ? (double)(L - 2) : 0.0;
         o[0] = tot[0] / n; o[1] = tot[1] / n; o[2] = tot[2] / n * 1000.0;   // root_dist, root_rot_dist, root_trans_dist
         o[3] = tot[3] / n; o[4] = tot[4] / n; o[5] = tot[5] / n * 1000.0;   // head_*
         double all = 0.0, body = 0.0;

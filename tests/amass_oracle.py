@@ -28,6 +28,11 @@ REFERENCE_DISTANCE = {"joints": 6.361e-08, "head_qpos": 6.688e-08, "head_vels": 
                       "global_head_rot_6d_diff": 3.102e-07, "global_head_trans": 6.688e-08, "global_head_trans_diff": 2.970e-06}
 
 
+# the same for head_vels on the sequences of rotation_edge_cases.head_sequences() (1, 2 and 40 frames; the reference's
+# get_head_vel cannot take one frame), against head_vel(..., float32=True); printed by tests/golden/make_head_vel_edges_golden.py
+HEAD_EDGES_REFERENCE_DISTANCE = (None, 1.037e-07, 1.425e-07)
+
+
 def corrected_fps(path, fps):
     if path.find("BMLhandball") >= 0:
         fps = 240
@@ -80,9 +85,16 @@ def _q_mul(a, b):
     return eval_oracle._q_mul(a, b)
 
 
-def head_vel(head_qpos, dt=1 / 30):
-    """get_head_vel (:111-137) in fp64 -> (head_vels [T, 6], the pairs that took the |1 -+ q0| < 1e-6 branch [T - 1] bool)."""
+def head_vel(head_qpos, dt=1 / 30, float32=False):
+    """get_head_vel (:111-137) in fp64 -> (head_vels [T, 6], the pairs that took the |1 -+ q0| < 1e-6 branch [T - 1] bool).
+    `float32` rounds head_qpos to float32 first: the reference hands get_head_vel a float32 tensor (:463-466) and the kernel
+    reads its own float32 quaternion, so at a quaternion whose rounding matters (w near 0, a relative rotation near pi) this is
+    the mode they are compared in.  A single frame has no pair: zero rows."""
     qp = np.asarray(head_qpos, np.float64)
+    if float32:
+        qp = qp.astype(np.float32).astype(np.float64)
+    if qp.shape[0] < 2:
+        return np.zeros((qp.shape[0], 6)), np.zeros(0, bool)
     rows, same = [], []
     for i in range(qp.shape[0] - 1):
         cur, nxt = qp[i], qp[i + 1]
@@ -112,14 +124,15 @@ def head_vel(head_qpos, dt=1 / 30):
     return np.vstack(rows), np.asarray(same, bool)
 
 
-def head_tracks(joints, head_rot):
+def head_tracks(joints, head_rot, float32=False):
     """joints [T, 22, 3] (after the floor shift and the downsampling), head_rot [T, 3, 3] -> the seven head arrays in fp64, plus
-    `same` (head_vel's flags), `quat` [T, 4] and `rot` (the input rotations)."""
+    `same` (head_vel's flags), `quat` [T, 4] and `rot` (the input rotations).  `float32`: head_vel's mode of that name (head_qpos
+    itself stays unrounded)."""
     joints, R = np.asarray(joints, np.float64), np.asarray(head_rot, np.float64)
     trans = joints[:, HEAD]
     quat = matrix_to_quaternion(R)
     qpos = np.concatenate([trans, quat], -1)
-    vels, same = head_vel(qpos)
+    vels, same = head_vel(qpos, float32=float32)
     diff = np.swapaxes(R[:-1], -1, -2) @ R[1:]
     return {"global_head_trans": trans, "global_head_rot_6d": R[:, :2].reshape(-1, 6), "head_qpos": qpos, "head_vels": vels,
             "global_head_rot_6d_diff": diff[:, :2].reshape(-1, 6), "global_head_trans_diff": trans[1:] - trans[:-1],

@@ -49,7 +49,11 @@ def _std(q):
 
 
 def quat_to_matrix(q):
+    """The rotation of q / |q|; identity below |q|^2 = 4 eps, as the reference's quaternion_matrix (transformation.py:1346-1370).
+    (np.where swaps (1, 0, 0, 0) in for such a row and leaves every other row's bits as they were.)"""
     q = np.asarray(q, np.float64)
+    tiny = (q * q).sum(-1, keepdims=True) < 4 * np.finfo(np.float64).eps
+    q = np.where(tiny, np.array([1.0, 0.0, 0.0, 0.0]), q)
     q = q / np.linalg.norm(q, axis=-1, keepdims=True)
     w, x, y, z = np.moveaxis(q, -1, 0)
     return np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
@@ -267,9 +271,15 @@ def evaluate_samples(rest_offsets, parents, local_aa, root_trans, gt_quat, gt_jp
         fc = floor_and_contacts(p, fps)
         floors.append(fc["offset_floor_height"])
         res.append(metrics(gq, gp, gt_floor_height, q, p, fc["offset_floor_height"]))
+    return res, np.asarray(floors, np.float32), best_per_group([r["mpjpe"] for r in res], group)
+
+
+def best_per_group(values, group):
+    """eval_egoego.py:434-446: per group id the first sample with the smallest value, by the reference's strict < (a NaN that
+    comes first stays, a later NaN never wins) -> {id: index}."""
     best = {}
-    for b in range(B):
-        g = group[b]
-        if g not in best or res[b]["mpjpe"] < res[best[g]]["mpjpe"]:
+    for b, v in enumerate(values):
+        g = int(group[b])
+        if g not in best or v < values[best[g]]:
             best[g] = b
-    return res, np.asarray(floors, np.float32), best
+    return best
