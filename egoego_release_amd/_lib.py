@@ -121,7 +121,7 @@ EXPORTS = ["egoego_abi_version", "egoego_last_error", "egoego_ctx_create", "egoe
            "egoego_s1_train_last_error", "egoego_s1_train_ctx_create", "egoego_s1_train_ctx_destroy", "egoego_s1_train_workspace_bytes",
            "egoego_s1_train_saves_bytes", "egoego_s1_train_forward", "egoego_s1_train_backward", "egoego_s1_train_dropout_mask",
            "egoego_s1_train_saved", "egoego_s1_headnet_loss_workspace_bytes", "egoego_s1_headnet_loss",
-           "egoego_s1_data_last_error", "egoego_s1_gravity_batch"]
+           "egoego_s1_data_last_error", "egoego_s1_gravity_batch", "egoego_s1_head_batch"]
 S1_TRAIN_SAVED = {"ffn_hidden": 0, "attn_prob": 1, "attn_out": 2, "attn_ln": 3, "layer_out": 4, "layer_in": 5, "head_hidden": 6}
 LOSS_L1, LOSS_L2 = 0, 1
 TRAIN_SITE_ATTN, TRAIN_SITE_FC, TRAIN_SITE_FFN = 0, 1, 2
@@ -300,6 +300,9 @@ def load():
     # pose, rows, offsets, sequences, seq ids, draw ids, B, window, seed, for_eval, planted start / rot / scale, ori_head_pose,
     # head_rot_mat, head_trans, seq_len, aligned_rot_mat, aligned_scale, floor_normal, start_t_idx, aug_scale, stream
     lib.egoego_s1_gravity_batch.argtypes = [vp, i32, vp, i32, vp, vp, i32, i32, u64, i32, vp, vp, vp] + [vp] * 9 + [vp]
+    # pose, vels, feats, rows, D, offsets, sequences, slam32, slam_trans64, slam offsets, slam rows, seq ids, draw ids, B, window, seed,
+    # for_eval, planted start, head_pose, head_vels, of, seq_len, start_t_idx, the six SLAM arrays, pose_len, stream
+    lib.egoego_s1_head_batch.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, u64, i32, vp] + [vp] * 12 + [vp]
     if lib.egoego_abi_version() != ABI_VERSION:
         raise EgoEgoHipError(f"ABI mismatch: library {lib.egoego_abi_version()} != binding {ABI_VERSION}")
     _lib = lib

@@ -897,14 +897,15 @@ def _quat_to_mat32(q):
 
 
 def load_slam(npy_path):
-    """AD load_data_from_droidslam: [T, 7] (xyz, quaternion w,x,y,z) -> trans [T, 3], rot [T, 3, 3] fp32, quat [T, 4]."""
-    d = np.load(npy_path)
+    """AD load_data_from_droidslam: [T, 7] (xyz, quaternion w,x,y,z), a .npy path or the array itself -> trans [T, 3], rot
+    [T, 3, 3] fp32, quat [T, 4]."""
+    d = np.load(npy_path) if isinstance(npy_path, (str, os.PathLike)) else np.asarray(npy_path)
     return d[:, :3], _quat_to_mat32(d[:, 3:]), d[:, 3:].astype(np.float32)
 
 
 def load_slam_res_and_align_first(npy_path, gt_head_pose):
-    """AD load_slam_res_and_align_first: rotate the SLAM trajectory so that its first rotation is the ground truth's, and move
-    its first position onto the ground truth's -> aligned trans [T, 3], rot [T, 3, 3], quat [T, 4]."""
+    """AD load_slam_res_and_align_first: rotate the SLAM trajectory (a .npy path or the [T, 7] array) so that its first rotation
+    is the ground truth's, and move its first position onto the ground truth's -> aligned trans [T, 3], rot [T, 3, 3], quat [T, 4]."""
     trans, rot, _ = load_slam(npy_path)
     gt_rot0 = _quat_to_mat32(gt_head_pose[:1, 3:])[0]
     p2g = torch.from_numpy(np.matmul(gt_rot0, rot[0].T)).float()[None]

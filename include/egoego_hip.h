@@ -892,6 +892,35 @@ int egoego_s1_gravity_batch(const float* d_pose, int n_rows, const int32_t* d_of
                             int32_t* d_seq_len, float* d_aligned_rot_mat, float* d_aligned_scale, float* d_floor_normal,
                             int32_t* d_start_t_idx, float* d_aug_scale, void* stream);
 
+/* HeadNet's training batches (egoego_s1_head_batch; added under ABI 8, purely additive): ARESHeadPoseDataset.__getitem__
+ * (ares_headpose_dataset.py:270-333, shared by the GIMO and real-world datasets) for the B samples of a batch in ONE launch on
+ * `stream`: no allocation, no host copy, no synchronisation, no workspace; every output is the caller's and is written whole.
+ * Nothing is computed: every output word is a copy of a table's word or a zero.  All tables and outputs are 16-byte aligned.
+ *   d_pose [n_rows][7], d_vels [n_rows][6] fp32 and d_offsets int32 [n_seqs + 1]: sequence k is rows offsets[k] .. offsets[k + 1]
+ *   - 1 (T_k of them); d_feats [n_rows - n_seqs][D] fp32: its F_k = T_k - 1 feature rows start at row offsets[k] - k; D a multiple
+ *   of 4.  Optional, NULL together: d_slam32 [n_slam_rows][29] fp32 (aligned trans 3 | aligned quat 4 | aligned rot 9 | original
+ *   quat 4 | original rot 9), d_slam_trans64 [n_slam_rows][3] fp64 (the original translation, not rounded) and d_slam_offsets int32
+ *   [n_seqs + 1] (L_k rows of sequence k).  d_seq_ids int32 [B], d_draw_ids int64 [B], d_start int32 [B] (planted starts) or NULL.
+ * The window, W = window: training has room = F_k - W + 1, n = W and start = (word 0 * room) >> 32 of Philox4x32-10 keyed by `seed`
+ * at the counter (draw id low, draw id high, 1, 0x48424154) (egoego_s1_gravity_batch's counters hold 0x47424154 there, dropout and
+ * the sampler's noise a number below 1000), or the planted start; for_eval has start = 0 (d_start is not read) and n = min(F_k, W).
+ *   d_head_pose [B][W + 1][7]: rows start .. start + n, rows > n zero; d_head_vels [B][W][6] and d_of [B][W][D]: rows start ..
+ *   start + n - 1, rows >= n zero; d_seq_len int32 [B] = n; d_start_t_idx int32 [B].  With the SLAM tables, the seven SLAM outputs
+ *   (NULL together, and with the tables): d_aligned_slam_trans [B][W + 1][3], d_aligned_slam_rot_quat [..][4], d_aligned_slam_rot_mat
+ *   [..][9], d_ori_slam_trans fp64 [..][3], d_ori_slam_rot_quat [..][4], d_ori_slam_rot_mat [..][9]: rows start .. of the track,
+ *   d_pose_len int32 [B] = clamp(L_k - start, 0, n + 1) of them, the rest zero.
+ * An EMPTY sample (seq_len 0, pose_len 0, start 0, every row zero) is written where the sequence id or its offsets do not describe
+ * rows inside the tables, where F_k < 1, where room < 1 in training, and where a planted start is outside 0 .. room - 1; nothing
+ * outside the tables is read.  EGOEGO_E_INVALID before any launch: window < 1, B < 1, D < 4 or D % 4 != 0, n_rows < 1, n_seqs < 1,
+ * a NULL required pointer, the SLAM tables or outputs given in part or one group without the other. */
+int egoego_s1_head_batch(const float* d_pose, const float* d_vels, const float* d_feats, int n_rows, int d_feats_dim,
+                         const int32_t* d_offsets, int n_seqs, const float* d_slam32, const double* d_slam_trans64,
+                         const int32_t* d_slam_offsets, int n_slam_rows, const int32_t* d_seq_ids, const int64_t* d_draw_ids, int B,
+                         int window, uint64_t seed, int for_eval, const int32_t* d_start, float* d_head_pose, float* d_head_vels,
+                         float* d_of, int32_t* d_seq_len, int32_t* d_start_t_idx, float* d_aligned_slam_trans,
+                         float* d_aligned_slam_rot_quat, float* d_aligned_slam_rot_mat, double* d_ori_slam_trans,
+                         float* d_ori_slam_rot_quat, float* d_ori_slam_rot_mat, int32_t* d_pose_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

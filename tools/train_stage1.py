@@ -6,11 +6,16 @@ normal_estimation.py (GravityNet) loop through egoego_release_amd.trainer.Stage1
     python tools/train_stage1.py --kind gravitynet --batches train.pt --val_batches val.pt ...  torch.save'd lists of batch dicts
     python tools/train_stage1.py --kind gravitynet --motion train_amass_smplh_motion.p [--val_motion test_amass_smplh_motion.p] ...
                                                       GravityNet on the head poses of a motion file (tools/process_amass.py)
+    python tools/train_stage1.py --kind headnet --data_root data --window 60 --batch_size 8 [--feature_cache feats.npz] ...
+                                                      HeadNet on the ARES files (the reference's scripts/train_headnet_on_ares.sh)
 
 A batch dict is what the reference's DataLoader yields (synthetic.make_stage1_train_batch documents the keys).  --motion builds
 GravityNet's batches on the GPU (egoego_release_amd.stage1_data.GravityBatches: random windows, one random rotation and scale per
 sample) from the file's `head_qpos`; without --val_motion the file is split by dataset name as the reference's divide_train_val
-does.  HeadNet's datasets (they need optical-flow features) are not part of this package.  Checkpoints <save_dir>/weights/train-<epoch>.pt hold the reference's keys ('epoch',
+does.  --data_root builds HeadNet's batches on the GPU (stage1_data.HeadBatches over stage1_data.load_ares_split: the train split's
+motion file, feature files and SLAM tracks under DIR; random windows) and validates on the test split's, unshuffled, as the
+reference's trainer does; --feature_cache PATH keeps the arrays read in PATH.train.npz / PATH.test.npz, so that a later run opens
+those two files only.  Checkpoints <save_dir>/weights/train-<epoch>.pt hold the reference's keys ('epoch',
 'transformer_encoder_state_dict', 'optimizer_state_dict', 'loss'): HeadFormer.load_state_dict and tools/run_egoego_demo.py take them.
 A GPU is required: there is no CPU path.
 """
@@ -36,7 +41,9 @@ def parse_opt(argv=None):
     p.add_argument("--val_batches", default=None)
     p.add_argument("--motion", default=None, help="gravitynet: a motion file (joblib / pickle) whose entries hold head_qpos [T, 7]")
     p.add_argument("--val_motion", default=None, help="a second motion file for validation (default: --motion split by dataset name)")
-    p.add_argument("--data_seed", type=int, default=0, help="--motion: the seed of the shuffle and of the augmentation draws")
+    p.add_argument("--data_root", default=None, help="headnet: the folder that holds ares_egoego_processed/ and ares/ (the ARES files)")
+    p.add_argument("--feature_cache", default=None, help="--data_root: keep the arrays read in PATH.train.npz and PATH.test.npz")
+    p.add_argument("--data_seed", type=int, default=0, help="--motion / --data_root: the seed of the shuffle and of the draws")
     p.add_argument("--synthetic_batches", type=int, default=8, help="synthetic batches per epoch when --batches is not given")
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--epochs", type=int, default=1000)
@@ -65,6 +72,10 @@ def parse_opt(argv=None):
         p.error("--motion feeds GravityNet only (HeadNet's data needs optical-flow features)")
     if opt.val_motion and not opt.motion:
         p.error("--val_motion needs --motion")
+    if opt.data_root and opt.kind != "headnet":
+        p.error("--data_root feeds HeadNet only (GravityNet trains from --motion)")
+    if opt.feature_cache and not opt.data_root:
+        p.error("--feature_cache needs --data_root")
     return opt
 
 
@@ -92,6 +103,19 @@ def motion_batches(opt, dev):
     return train, (GravityBatches(data, opt.batch_size, train=False, shuffle=False, names=val_names, **kw) if val_names else None)
 
 
+def ares_batches(opt, dev):
+    """-> (train, val) HeadBatches of --data_root's train and test splits (val None when the test split has no motion file)."""
+    from egoego_release_amd.stage1_data import HeadBatches, load_ares_split
+    cache = lambda split: f"{opt.feature_cache}.{split}.npz" if opt.feature_cache else None  # noqa: E731
+    kw = dict(window=opt.window, seed=opt.data_seed, device=dev)
+    train = HeadBatches(load_ares_split(opt.data_root, True, opt.window, cache("train")), opt.batch_size, **kw)
+    test_file = os.path.join(opt.data_root, "ares_egoego_processed", "test_ares_smplh_motion.p")
+    if not (os.path.exists(test_file) or (cache("test") and os.path.exists(cache("test")))):
+        return train, None
+    val = load_ares_split(opt.data_root, False, opt.window, cache("test"))
+    return train, (HeadBatches(val, opt.batch_size, train=False, shuffle=False, **kw) if val else None)
+
+
 def main(argv=None):
     opt = parse_opt(argv)
     if not torch.cuda.is_available():
@@ -102,6 +126,8 @@ def main(argv=None):
     load = lambda path: torch.load(path, map_location="cpu")  # noqa: E731
     if opt.motion:
         train, val = motion_batches(opt, dev)
+    elif opt.data_root:
+        train, val = ares_batches(opt, dev)
     elif opt.batches:
         train, val = load(opt.batches), (load(opt.val_batches) if opt.val_batches else None)
     else:
